@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- fastq_count hot path on MI355X: Gbases/s and % of the HBM roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` IS the number of ranks.  Under a launcher (WORLD_SIZE in the environment) the rank checks WORLD_SIZE == N and
@@ -15,9 +15,12 @@ counter-based generator), plus -- for N > 1 -- the one sum all-reduce of the
 count vector, plus the fetch of the counts to the host.  Inputs are resident in
 HBM when the timed region starts (inflate / PCIe are host work).
 Weak scaling: every rank holds its own 1e9-read shard (configs[4]: 8e9 reads on 8 GPUs).
-Rank 0 prints ONE JSON line.  Its `extra` object (bench_extra.py) holds what the headline does not: the exact check of
-the headline launch, the kernels of the other named configurations (K1L, K2, K3 + K4, K5) with their own
-roofline fractions, and end-to-end legs through the CLI binaries with the reference binary timed beside each.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set up, warm up, time the K steps,
+print.  `--full` adds, after the timed region, the closed-form check of the counts, the mixed-length K1 run (`frac_ragged`),
+the CPU baseline and the `extra` object (bench_extra.py): the exact check of the headline launch, the kernels of the other
+named configurations (K1L, K2, K3 + K4, K5) with their own roofline fractions, and end-to-end legs through the CLI binaries
+with the reference binary timed beside each.  `--dump-outputs DIR` writes the counts of the last timed step as
+DIR/<name>.npy (float64): seqlen, total, q20, q30, and qual_hist with --full-matrix.
 """
 import argparse
 import ctypes as C
@@ -44,9 +47,12 @@ def parse():
     ap.add_argument("--reads", type=float, default=1e9, help="reads per GPU (BASELINE configs[1])")
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--full-matrix", action="store_true", help="also build Quality[128][512] (kthread -L path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="headline only: skip the exact check, the other kernels and the end-to-end legs")
-    ap.add_argument("--no-ragged", action="store_true", help="skip the mixed-length K1 run behind the timed region (PMC passes: every k_tally_scan launch is then the headline's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the counts of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run the checks and the other measurements: "
+                                                        "closed-form check, mixed-length K1 run, CPU baseline, extra legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the exact check, the other kernels and the end-to-end legs")
+    ap.add_argument("--no-ragged", action="store_true", help="with --full: skip the mixed-length K1 run behind the timed region (PMC passes: every k_tally_scan launch is then the headline's)")
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="target wall time of the CPU baseline leg")
     ap.add_argument("--rank-timeout", type=float, default=3000.0, help="launcher: seconds the N ranks may take together")
     return ap.parse_args()
@@ -248,10 +254,20 @@ def cpu_baseline(read_len, target_s):
         shutil.rmtree(td, ignore_errors=True)
 
 
+def dump_outputs(d, out):
+    """What a caller of the timed path receives (ShardedTally.step), one float64 .npy per array; counts below 2^53 are exact."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a))
     rank = int(os.environ.get("RANK", 0))
@@ -322,13 +338,15 @@ def main():
     dt = shard.max_over_ranks(time.perf_counter() - t0, be.device)
     k_mine = sum(kernel_ms) / max(1, len(kernel_ms))
     k_ranks = shard.gather_floats(k_mine, be.device)   # every rank's mean kernel time, in rank order
+    if a.dump_outputs and rank == 0:   # the job's counts, identical on every rank
+        dump_outputs(a.dump_outputs, out)
 
     # ---- the same kernel on reads of MIXED lengths (after the timed region; rank 0's figure is reported) --------------------
     # The headline's reads are all 150 bp, which lets K1's offset pass add 1,024 equal lengths at once; trimmed data does not.
     # Same resident quality bytes, offsets of lengths drawn like adapter / quality-trimmed reads: 70 % untouched (150), the rest
     # uniform on 30..149.  Checked in closed form against the lengths themselves.
     ragged = None
-    if be.name == "hip" and not a.full_matrix and n >= 1000 and not a.no_ragged and L > 30:
+    if a.full and be.name == "hip" and not a.full_matrix and n >= 1000 and not a.no_ragged and L > 30:
         g0 = torch.Generator(device="cuda").manual_seed(2025 + rank)
         rl = torch.randint(30, L, (n,), device="cuda", generator=g0, dtype=torch.int64)   # 30 .. L-1: never beyond a read's bytes
         keep = torch.rand(n, device="cuda", generator=g0) < 0.7
@@ -357,9 +375,10 @@ def main():
 
     # ---- result checks (after the timed region) ------------------------------------------------
     # closed form: every record of every rank counted once, at its length
-    job.check_closed_form(out, n, L)
     extra = {}
-    if not a.no_extra:
+    if a.full:
+        job.check_closed_form(out, n, L)
+    if a.full and not a.no_extra:
         # exact: this rank's K1 counts against an independent kernel (K1L) over the same resident bytes, and three
         # 2e5-read windows against the CPU oracle (bench_extra.exact_check)
         import bench_extra
@@ -372,7 +391,7 @@ def main():
     del d_qual, d_off
     if be.name == "hip":
         torch.cuda.empty_cache()
-    if world == 1 and not a.no_extra:
+    if a.full and world == 1 and not a.no_extra:
         extra["plain_traffic"] = bench_extra.plain_traffic()
         extra["kernel_legs"] = bench_extra.kernel_legs(ctx)
         try:
@@ -416,7 +435,7 @@ def main():
                          "algorithmic_bytes_per_launch": alg_bytes,
                          "frac_ragged": ragged["frac"] if ragged else None, "ragged": ragged},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(L, a.cpu_seconds)
             except Exception as e:  # noqa: BLE001  (a reported baseline must not take the GPU line down)

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r05; out=gpurun_out/r05/ab_k1_sched.txt; : > $out
 for v in 811 812 811 812; do
   echo "== HPN_K1_VARIANT=$v" >> $out
-  HPN_LIB=$PWD/highperformancengs_amd/testhooks/libhpngs.so HPN_K1_VARIANT=$v python bench.py --no-extra --no-cpu-baseline --steps 10 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']; print('frac', r['frac'], 'kernel_ms', r['kernel_ms'], '| ragged frac', r['frac_ragged'], 'kernel_ms', r['ragged']['kernel_ms'])" >> $out
+  HPN_LIB=$PWD/highperformancengs_amd/testhooks/libhpngs.so HPN_K1_VARIANT=$v python bench.py --full --no-extra --no-cpu-baseline --steps 10 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']; print('frac', r['frac'], 'kernel_ms', r['kernel_ms'], '| ragged frac', r['frac_ragged'], 'kernel_ms', r['ragged']['kernel_ms'])" >> $out
 done
 for v in 811 812; do
   echo "== uniform 100..151, HPN_K1_VARIANT=$v" >> $out

@@ -7,7 +7,7 @@ set -x
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/r05
 mkdir -p $O /tmp/abw
-[ -z "$NOBENCH" ] && python bench.py > $O/bench.json 2> $O/bench.err
+[ -z "$NOBENCH" ] && python bench.py --full > $O/bench.json 2> $O/bench.err
 g++ -O2 -std=c++17 scripts/bam_synth.cpp -o /tmp/abw/bam_synth -lz -lpthread
 [ -f /tmp/abw/a.bam ] || /tmp/abw/bam_synth /tmp/abw/a.bam --targets chr1:120000000:14000000 12 >/dev/null 2>&1
 cd /tmp && export TMPDIR=/tmp

@@ -8,7 +8,7 @@ set -x
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/r06
 mkdir -p $O
-[ -z "$NOBENCH" ] && python bench.py > $O/bench.json 2> $O/bench.err
+[ -z "$NOBENCH" ] && python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 prof() {   # name, command...
   n=$1; shift

@@ -5,13 +5,16 @@ Run in the build container only (needs oracle/_ref/*, i.e. `make -C oracle ref`,
 which compiles the reference tools from /root/reference).  The inputs and the
 reference's outputs are committed as data; no reference source is stored.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py              # everything below
+    python tests/golden/make_golden.py c4_synth     # tests/golden/c4_synth/ only
 
 Layout written:
     tests/golden/fastq/*            small FASTQ inputs (plain / gzip)
     tests/golden/bam/*              small BAM + BAI inputs
     tests/golden/expected/<case>/   stdout, and every file the tool wrote
     tests/golden/manifest.json      case list: tool, argv, inputs, outputs
+    tests/golden/c4_synth/<case>/   tests/test_c4_synth.py: what bam2depth / bam_sliding_count printed for
+                                    the BAM files scripts/bam_synth.cpp --targets writes (inputs made by the test)
 """
 import ctypes
 import gzip
@@ -192,6 +195,37 @@ def make_bam_inputs():
 
 CASES = []
 
+C4 = os.path.join(HERE, "c4_synth")
+# tests/test_c4_synth.py's two instances: (case, BAM name, targets [(name, length, reads)], window, tools)
+C4_CASES = [("targets", "t.bam", [("chr1", 300000, 40000), ("chrTiny", 16569, 3300), ("chrEmpty", 5000, 0), ("chrX", 120000, 9000)],
+             2000, ["bam2depth", "bam_sliding_count"]),
+            ("gc_f32", "g.bam", [("chrBig", 2_000_000, 260_000), ("chrS", 50_000, 1000)], 3_000_000, ["bam_sliding_count"])]
+
+
+def make_c4_synth():
+    """Run the reference tools on the generator's BAM files; keep their reports (gzip-compressed past 64 KiB) and the
+    MD5 of the inflated BAM they read, which the test checks its own generator run against."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import c4
+    shutil.rmtree(C4, ignore_errors=True)
+    for case, bam, tg, W, tools in C4_CASES:
+        out_dir = os.path.join(C4, case)
+        os.makedirs(out_dir)
+        with tempfile.TemporaryDirectory() as td:
+            c4.synth(td, bam, tg, 3)
+            w(os.path.join(out_dir, "bam_inflated.md5"), hashlib.md5(gzip.decompress(open(os.path.join(td, bam), "rb").read())).hexdigest() + "\n")
+            outs = {"bam2depth": [bam + ".1.bedGraph", "d.1.depth"], "bam_sliding_count": ["s.txt"]}
+            for tool in tools:
+                subprocess.run([os.path.join(REF, tool), "-w", str(W), "-o", "s" if tool == "bam_sliding_count" else "d", bam],
+                               cwd=td, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+                for f in outs[tool]:
+                    data = open(os.path.join(td, f), "rb").read()
+                    if len(data) > (64 << 10):
+                        gz(os.path.join(out_dir, f + ".gz"), data, 9)
+                    else:
+                        w(os.path.join(out_dir, f), data)
+        print(f"c4_synth/{case}: {sorted(os.listdir(out_dir))}")
+
 
 def run_case(name, tool, args, inputs, cwd_outputs=True, stdin=None, unordered=False):
     """Run a reference tool in a scratch dir holding copies of `inputs`.
@@ -333,7 +367,11 @@ def main():
         json.dump({"generator": "tests/golden/make_golden.py",
                    "reference_tools": "oracle/_ref (compiled from /root/reference by oracle/Makefile)",
                    "cases": CASES}, f, indent=1)
+    make_c4_synth()
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["c4_synth"]:   # only tests/golden/c4_synth/
+        make_c4_synth()
+    else:
+        main()

@@ -41,3 +41,18 @@ def test_one_rank_prints_one_complete_line():
     r = j["roofline"]
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and 0 < r["frac"] < 1 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     assert len(r["kernel_ms_per_rank"]) == 1 and j["unit"] == "Gbases/s" and j["dtype"] == "u8"
+
+
+def test_dump_outputs_are_the_counts_of_the_timed_path(tmp_path):
+    """--dump-outputs: the last timed step's counts as float64 .npy files, equal to the CPU oracle's on the same seeded reads."""
+    import numpy as np
+    import orc
+    p = _bench(["--gpus", "1", "--dump-outputs", str(tmp_path)] + SMALL)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in ("seqlen", "total", "q20", "q30")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    _seq, qual, off = orc.synth_soa(12345, 0, 200000, 150, 150)
+    rc, want = orc.count_soa(qual, off)
+    s = want.summary()
+    assert rc == 0 and np.array_equal(got["seqlen"], np.asarray(want.seqlen, np.float64))
+    assert (got["total"], got["q20"], got["q30"]) == (s.sum, s.q20, s.q30)

@@ -84,3 +84,40 @@ def test_torchrun_launch_still_works():
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     j = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["config"]["launcher"] == "torchrun"
+
+
+def _line(p):
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_dump_outputs_hold_the_last_steps_counts(n, tmp_path):
+    """--dump-outputs DIR: the counts the timed path returned in its last step, one float64 .npy per array, the same from run
+    to run (the inputs are seeded)."""
+    import numpy as np
+    for run in ("a", "b"):
+        j = _line(_bench(["--gpus", str(n), "--steps", "3", "--warmup", "1", "--reads", "3000", "--read-len", "60",
+                          "--dump-outputs", str(tmp_path / run)]))
+        assert j["steps"] == 3 and j["warmup"] == 1
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["q20.npy", "q30.npy", "seqlen.npy", "total.npy"] and names == sorted(os.listdir(tmp_path / "b"))
+    got = {k[:-4]: np.load(tmp_path / "a" / k) for k in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["seqlen"].shape == (512,) and got["seqlen"][60] == n * 3000 and got["seqlen"].sum() == n * 3000
+    assert got["total"] == n * 3000 * 60 and 0 < got["q30"] <= got["q20"] <= got["total"]
+    for k in names:
+        assert np.array_equal(np.load(tmp_path / "a" / k), np.load(tmp_path / "b" / k))
+
+
+def test_plain_run_is_the_headline_only_and_full_adds_the_checks():
+    """A plain run sets up, warms up, times the steps and prints: no CPU baseline, no extra legs.  --full runs what lies
+    behind the timed region (here the closed-form check; the stub backend has no kernels for the other legs)."""
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "3000", "--read-len", "60"]
+    j = _line(_bench(args))
+    assert "cpu_baseline" not in j and "extra" not in j and j["roofline"]["ragged"] is None
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(j)
+    j = _line(_bench(args + ["--full", "--no-extra", "--no-cpu-baseline"]))
+    assert j["steps"] == 2 and "extra" not in j
