@@ -37,6 +37,19 @@ class TextInfo(C.Structure):
                 ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SampleRule(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("fasta", C.c_uint32), ("seed_add", C.c_uint32), ("threshold", C.c_uint32),
+                ("picks", C.c_void_p), ("n_picks", C.c_uint64), ("first_ordinal", C.c_uint64)]
+
+
+class SampleInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_kept", C.c_uint64), ("n_bytes", C.c_uint64), ("carry_bytes", C.c_uint64),
+                ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SAMPLE_FRACTION, SAMPLE_PICKS = 1, 2
+
+
 class TextPiece(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -112,6 +125,7 @@ SYMBOLS = [
     ("hpn_fastq_text_count_inplace", _int, [_vp, _vp, _u64, _int, _u32, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_records", _int, [_vp, _vp, _u64, _int, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_trim", _int, [_vp, _vp, _u64, _int, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
+    ("hpn_fastq_text_sample", _int, [_vp, _vp, _u64, _int, C.POINTER(SampleRule), _vp, _u64, _vp, _u64, C.POINTER(SampleInfo)]),
     ("hpn_fastq_text_piece_lines", _int, [_vp, _vp, _u64, _u32, _u64, _int, C.POINTER(TextPiece)]),
     ("hpn_fastq_text_piece_count", _int, [_vp, _u64, _u32, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_piece_trim", _int, [_vp, _u64, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
@@ -173,7 +187,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 1:
+    if L.hpn_abi_version() != 2:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

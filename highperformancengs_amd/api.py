@@ -228,6 +228,27 @@ class Context:
                                             C.byref(info)), "hpn_fastq_text_trim")
         return out[:0 if info.irregular else int(info.n_bytes)].tobytes(), info
 
+    def fastq_text_sample(self, chunk, last=False, *, threshold=None, seed_add=0, picks=None, fasta=False, first_ordinal=0, out_cap=None):
+        """One chunk of FASTQ text -> (sampled text bytes, kept 0-based ordinals, hpn_sample_info): hpn_fastq_text_sample.
+        Exactly one rule: `threshold` (0 .. 2^24, with `seed_add`) or `picks` (sorted uint64 ordinals over the whole stream)."""
+        if (threshold is None) == (picks is None):
+            raise ValueError("give threshold= or picks=")
+        chunk, n = self._text(chunk)
+        rule = _lib.SampleRule(fasta=int(bool(fasta)), first_ordinal=first_ordinal)
+        if picks is None:
+            rule.mode, rule.seed_add, rule.threshold = _lib.SAMPLE_FRACTION, seed_add & 0xFFFFFFFF, threshold
+        else:
+            picks = np.ascontiguousarray(picks, np.uint64)
+            rule.mode, rule.picks, rule.n_picks = _lib.SAMPLE_PICKS, picks.ctypes.data if picks.size else None, picks.size
+        info = _lib.SampleInfo()
+        out = np.zeros(7 * (n + 8192) if out_cap is None else out_cap, np.uint8)
+        kept = np.zeros((n + 8192) // 4, np.uint64)
+        self._ck(self.L.hpn_fastq_text_sample(self.h, _ptr(chunk) if n else None, n, int(bool(last)), C.byref(rule), _ptr(out) if out.size else None,
+                                              out.size, _ptr(kept), kept.size, C.byref(info)), "hpn_fastq_text_sample")
+        if info.irregular:
+            return b"", kept[:0], info
+        return out[:int(info.n_bytes)].tobytes(), kept[:int(info.n_kept)].copy(), info
+
     # ---- one stream framed by several contexts: pieces ---------------------------------
     def text_piece_lines(self, text, head, own_bytes, last=False):
         """First half of a piece (hpn_fastq_text_piece_lines): text = head byte + piece + tail; returns hpn_text_piece."""

@@ -1,7 +1,10 @@
 // hpn_text.hip -- C ABI of the raw-text front end: device-side framing of FASTQ text
 // (the 4 x gzgets loops of fastq_count.c:112-118 and fastq_trim.c:67-89), feeding the
-// tally kernels or writing the trimmed text.  Kernels: kernels/fastq_text.hip.
+// tally kernels, writing the trimmed text or a subsample of the records (gzfastq_sample.c).
+// Kernels: kernels/fastq_text.hip, kernels/fastq_sample.hip.
 #include <string.h>
+
+#include <algorithm>
 
 #include "hpn_ctx.hpp"
 
@@ -20,6 +23,15 @@ hipError_t launch_text_records(const uint32_t *d_nl, uint32_t begin, uint32_t en
                                u64 *d_status, uint32_t *d_state, hipStream_t st);
 uint64_t text_tiles1(uint32_t begin, uint32_t end);
 uint64_t text_tiles2(uint32_t nl_cap);
+// kernels/fastq_sample.hip
+uint64_t sample_tiles(uint32_t nl_cap);
+hipError_t launch_sample_select(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last,
+                                uint32_t carry_cap, uint32_t mode, uint32_t fasta, uint32_t seed_add, uint32_t threshold,
+                                const uint64_t *d_picks, uint32_t n_picks, uint64_t ordinal0, uint32_t nl_cap, uint64_t *d_off,
+                                uint64_t *d_keep, u64 *d_status, uint32_t *d_state, hipStream_t st);
+hipError_t launch_sample_write(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, const uint64_t *d_off,
+                               const uint64_t *d_keep, uint32_t n_kept, uint32_t n, uint32_t n_lines, uint32_t unterminated,
+                               uint64_t ordinal0, uint32_t fasta, uint8_t *d_out, int n_cu, hipStream_t st);
 }  // namespace hpn
 
 using namespace hpn;
@@ -28,13 +40,20 @@ namespace {
 
 constexpr uint32_t kCarryCap = 8192;  // room in front of a chunk for the unfinished record of the previous one
 constexpr int kStateWords = 16;       // kernels/fastq_text.hip: kTs*
-enum { kTsLines = 0, kTsRecs, kTsFlags, kTsUnterminated, kTsConsumed, kTsTotalLo, kTsTotalHi, kTsErr, kTsTicket1, kTsTicket2, kTsOwnLines };
+enum { kTsLines = 0, kTsRecs, kTsFlags, kTsUnterminated, kTsConsumed, kTsTotalLo, kTsTotalHi, kTsErr, kTsTicket1, kTsTicket2, kTsOwnLines, kTsKept };
 
 struct Framed {
     uint32_t begin = 0, n = 0;
     uint64_t total = 0;
     const uint8_t *slot = nullptr;
     const uint32_t *nlp = nullptr;   // pieces: the first record's four line ends
+    uint32_t n_kept = 0, n_lines = 0, unterminated = 0;   // sample
+};
+
+// hpn_fastq_text_sample: the rule as the select kernel takes it (records are selected instead of scanned by k_text_records)
+struct SampleRun {
+    const hpn_sample_rule *rule;
+    uint64_t ordinal0;   // 0-based ordinal of the chunk's first record
 };
 
 // Copy the chunk behind the carried-over bytes, index the lines, validate and scan the
@@ -44,7 +63,7 @@ struct Framed {
 // overwrite the text as soon as the call returns.  (The gzip route's text is on the device already: the copy into a slot was
 // 2 x 15.9 GB of traffic per 9.3 GB batch, 5.7 ms of its ~250: profiles/r06/kernel_stats_gz_tool_members.csv, __amd_rocclr_copyBuffer.)
 int text_frame(hpn_ctx *c, const void *text, uint64_t nbytes, int last, bool trim, uint32_t S, uint32_t E,
-               hpn_text_info *info, Framed *f, bool in_place = false)
+               hpn_text_info *info, Framed *f, bool in_place = false, const SampleRun *sample = nullptr)
 {
     if (!c->t_open) return fail(c, HPN_E_STATE, "hpn_fastq_text_begin first (or the stream was closed by an irregular chunk)");
     if (nbytes >= (1ull << 31) - 2 * kCarryCap) return fail(c, HPN_E_ARG, "chunk of %llu bytes (limit 2^31 - 16 KiB)", (unsigned long long)nbytes);
@@ -70,10 +89,33 @@ int text_frame(hpn_ctx *c, const void *text, uint64_t nbytes, int last, bool tri
     const uint32_t nl_cap = (((end - begin) / 4u) + 16u) & ~3u;
     if ((rc = scratch_reserve(c, c->t_nl, (size_t)nl_cap * sizeof(uint32_t) + 64)) != HPN_OK) return rc;
     if ((rc = scratch_reserve(c, c->t_off, ((size_t)nl_cap / 4 + 2) * sizeof(uint64_t))) != HPN_OK) return rc;
-    if ((rc = scratch_reserve(c, c->t_status, (text_tiles1(begin, end) + text_tiles2(nl_cap)) * sizeof(u64))) != HPN_OK) return rc;
+    const uint64_t tiles2 = sample && sample_tiles(nl_cap) > text_tiles2(nl_cap) ? sample_tiles(nl_cap) : text_tiles2(nl_cap);
+    if ((rc = scratch_reserve(c, c->t_status, (text_tiles1(begin, end) + tiles2) * sizeof(u64))) != HPN_OK) return rc;
+    uint32_t n_picks = 0;
+    if (sample) {
+        if ((rc = scratch_reserve(c, c->t_keep, ((size_t)nl_cap / 4 + 2) * sizeof(uint64_t))) != HPN_OK) return rc;
+        const hpn_sample_rule *r = sample->rule;
+        if (r->mode == HPN_SAMPLE_PICKS && r->n_picks) {  // the part of the list that can fall into this chunk: at most nl_cap / 4 records
+            const uint64_t *lo = std::lower_bound(r->picks, r->picks + r->n_picks, sample->ordinal0);
+            const uint64_t beyond = sample->ordinal0 + nl_cap / 4u;   // (wraps only at the very end of the 64-bit ordinals)
+            const uint64_t *hi = beyond < sample->ordinal0 ? r->picks + r->n_picks : std::lower_bound(lo, r->picks + r->n_picks, beyond);
+            n_picks = (uint32_t)(hi - lo);
+            if (n_picks) {
+                if ((rc = scratch_reserve(c, c->t_picks, (size_t)n_picks * sizeof(uint64_t))) != HPN_OK) return rc;
+                HPN_HIP(c, hipMemcpyAsync(c->t_picks.p, lo, (size_t)n_picks * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+            }
+        }
+    }
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamText], c->stream));
-    HPN_HIP(c, launch_text_frame(slot, begin, end, last, trim, S, E, kCarryCap - 64, (uint32_t *)c->t_nl.p, nl_cap,
-                                 (uint64_t *)c->t_off.p, (u64 *)c->t_status.p, c->t_state, c->stream));
+    if (sample) {
+        const hpn_sample_rule *r = sample->rule;
+        HPN_HIP(c, launch_text_lines(slot, begin, end, last, 0u, (uint32_t *)c->t_nl.p, nl_cap, (u64 *)c->t_status.p, c->t_state, c->stream));
+        HPN_HIP(c, launch_sample_select(slot, (const uint32_t *)c->t_nl.p, begin, end, last, kCarryCap - 64, r->mode, r->fasta ? 1u : 0u, r->seed_add,
+                                        r->threshold, (const uint64_t *)c->t_picks.p, n_picks, sample->ordinal0, nl_cap, (uint64_t *)c->t_off.p,
+                                        (uint64_t *)c->t_keep.p, (u64 *)c->t_status.p + text_tiles1(begin, end), c->t_state, c->stream));
+    } else
+        HPN_HIP(c, launch_text_frame(slot, begin, end, last, trim, S, E, kCarryCap - 64, (uint32_t *)c->t_nl.p, nl_cap,
+                                     (uint64_t *)c->t_off.p, (u64 *)c->t_status.p, c->t_state, c->stream));
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamText], c->stream));
     c->ev_valid[kFamText] = true;
     HPN_HIP(c, hipMemcpyAsync(c->h_tstate, c->t_state, kStateWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -92,6 +134,7 @@ int text_frame(hpn_ctx *c, const void *text, uint64_t nbytes, int last, bool tri
     f->n = h[kTsRecs];
     f->total = ((uint64_t)h[kTsTotalHi] << 32) | h[kTsTotalLo];
     f->slot = slot;
+    f->n_kept = h[kTsKept], f->n_lines = h[kTsLines], f->unterminated = h[kTsUnterminated];
     info->n_records = f->n;
     info->n_bytes = f->total;
     info->carry_bytes = last ? 0 : end - h[kTsConsumed];
@@ -119,6 +162,7 @@ int hpn_fastq_text_begin(hpn_ctx *c)
     c->t_carry = 0;
     c->t_tail = 0;
     c->t_carry_saved = false;
+    c->t_records = 0;
     return HPN_OK;
 }
 
@@ -187,6 +231,43 @@ int hpn_fastq_text_trim(hpn_ctx *c, const void *text, uint64_t nbytes, int last,
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
     c->ev_valid[kFamTrim] = true;
     HPN_HIP(c, hipMemcpyAsync(out_text, c->t_out.p, f.total, hipMemcpyDefault, c->stream));
+    HPN_HIP(c, hipStreamSynchronize(c->stream));
+    return HPN_OK;
+}
+
+int hpn_fastq_text_sample(hpn_ctx *c, const void *text, uint64_t nbytes, int last, const hpn_sample_rule *rule, void *out_text,
+                          uint64_t out_cap, uint64_t *kept_ordinals, uint64_t kept_cap, hpn_sample_info *info)
+{
+    if (!c || !info || !rule) return HPN_E_ARG;
+    if (rule->mode != HPN_SAMPLE_FRACTION && rule->mode != HPN_SAMPLE_PICKS) return fail(c, HPN_E_ARG, "unknown sample mode %u", rule->mode);
+    if (rule->mode == HPN_SAMPLE_FRACTION && rule->threshold > (1u << 24)) return fail(c, HPN_E_DOMAIN, "threshold %u beyond 2^24", rule->threshold);
+    if (rule->mode == HPN_SAMPLE_PICKS && rule->n_picks && !rule->picks) return fail(c, HPN_E_ARG, "picks is NULL");
+    HPN_HIP(c, hipSetDevice(c->device));
+    memset(info, 0, sizeof *info);
+    Framed f;
+    hpn_text_info ti;
+    const uint64_t ordinal0 = rule->first_ordinal + c->t_records;
+    const SampleRun run{rule, ordinal0};
+    int rc = text_frame(c, text, nbytes, last, false, 0, 0, &ti, &f, false, &run);
+    if (rc != HPN_OK) return rc;
+    info->irregular = ti.irregular;
+    if (ti.irregular) return HPN_OK;
+    if (f.total > out_cap || (f.total && !out_text) || (kept_ordinals && f.n_kept > kept_cap)) {
+        c->t_open = false;
+        return fail(c, HPN_E_CAPACITY, "the sample of this chunk needs %llu bytes and %u ordinals, out_cap is %llu, kept_cap %llu",
+                    (unsigned long long)f.total, f.n_kept, (unsigned long long)out_cap, (unsigned long long)(kept_ordinals ? kept_cap : 0));
+    }
+    info->n_records = f.n, info->n_kept = f.n_kept, info->n_bytes = f.total, info->carry_bytes = ti.carry_bytes;
+    c->t_records += f.n;
+    if (f.n_kept == 0) return HPN_OK;
+    if ((rc = scratch_reserve(c, c->t_out, f.total + 64)) != HPN_OK) return rc;
+    HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
+    HPN_HIP(c, launch_sample_write(f.slot, (const uint32_t *)c->t_nl.p, f.begin, (const uint64_t *)c->t_off.p, (const uint64_t *)c->t_keep.p, f.n_kept,
+                                   f.n, f.n_lines, f.unterminated, ordinal0, rule->fasta ? 1u : 0u, (uint8_t *)c->t_out.p, c->n_cu, c->stream));
+    HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
+    c->ev_valid[kFamTrim] = true;
+    HPN_HIP(c, hipMemcpyAsync(out_text, c->t_out.p, f.total, hipMemcpyDefault, c->stream));
+    if (kept_ordinals) HPN_HIP(c, hipMemcpyAsync(kept_ordinals, c->t_keep.p, (size_t)f.n_kept * sizeof(uint64_t), hipMemcpyDefault, c->stream));
     HPN_HIP(c, hipStreamSynchronize(c->stream));
     return HPN_OK;
 }

@@ -23,19 +23,15 @@
 //
 // Bound: HBM (one read of the text per kernel, 4 B per line, 8 B per record);
 // in the tools the PCIe copy of the text is ~100x slower than these kernels.
-#include "scan.hpp"
+#include "text_common.hpp"
 
 namespace hpn {
 
-constexpr int kTxtThreads = 256;
 constexpr int kLinesThreads = 512;                              // k_text_lines (256: 0.295, 512: 0.266, 1024: 0.258 ms per GiB)
 constexpr int kTxtRows = 16;                                    // 16-byte words per thread
 constexpr uint32_t kTxtTile = kLinesThreads * kTxtRows * 16;    // bytes per workgroup of k_text_lines
 constexpr int kRecPerThread = 4;
 constexpr uint32_t kRecTile = kTxtThreads * kRecPerThread;      // records per workgroup
-
-// device state block (uint32 words), zeroed before every chunk
-enum { kTsLines = 0, kTsRecs, kTsFlags, kTsUnterminated, kTsConsumed, kTsTotalLo, kTsTotalHi, kTsErr, kTsTicket1, kTsTicket2, kTsOwnLines, kTsWords = 16 };
 
 __device__ __forceinline__ uint32_t zero_bytes(uint32_t x)  // 0x80 in exactly the bytes of x that are 0
 {
@@ -364,22 +360,6 @@ __global__ __launch_bounds__(kTxtThreads) void k_text_records(const uint32_t *__
             st[kTsTotalLo] = (uint32_t)run;
             st[kTsTotalHi] = (uint32_t)(run >> 32);
         }
-    }
-}
-
-// 16 lanes copy one span: 16-byte unaligned pieces, the last one overlapping its
-// predecessor; spans shorter than 16 bytewise.
-__device__ __forceinline__ void copy_span(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint32_t cnt, int sub)
-{
-    if (cnt >= 16u) {
-        for (uint32_t i = 16u * (uint32_t)sub; i < cnt; i += 256u) {
-            const uint32_t o = min(i, cnt - 16u);
-            u32 v;
-            __builtin_memcpy(&v, src + o, 16);
-            __builtin_memcpy(dst + o, &v, 16);
-        }
-    } else if ((uint32_t)sub < cnt) {
-        dst[sub] = src[sub];
     }
 }
 

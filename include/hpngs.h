@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 1
+#define HPN_ABI_VERSION 2
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -247,6 +247,47 @@ int hpn_fastq_text_records(hpn_ctx *ctx, const void *text, uint64_t nbytes, int 
  * capacity out_cap; nbytes + 8192 always suffices). */
 int hpn_fastq_text_trim(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, int32_t S, int32_t E,
                         void *out_text, uint64_t out_cap, hpn_text_info *info);
+
+/* gzfastq_sample.c: a subsample of the stream's records as text.  Records are framed as readNextNode frames them
+ * (:315-335, the four gzgets of fastq_trim.c); record i (1-based over the whole stream, counted across the chunks since
+ * hpn_fastq_text_begin) is kept by one of two rules and written as printNode writes it (:30-37): "name_i\nseq\n+\n" + the
+ * quality line as read (a last line without '\n' stays without), or with `fasta` ">name_i\nseq\n" (the name keeps its '@').
+ *   HPN_SAMPLE_FRACTION  filter_reads (:150-153): keep iff ((X31(name) + seed_add) & 0xffffff) < threshold, X31 the string hash
+ *                        of khash.h:336-341 over the whole name line without its '\n' (bytes as signed chars).  The
+ *                        reference's test (k & 0xffffff) / 2^24 < frac is this one with threshold = ceil(frac * 2^24).
+ *   HPN_SAMPLE_PICKS     get_number_from_file (:253-264): keep iff the record's 0-based ordinal is in `picks`, a sorted list
+ *                        of ordinals over the whole stream in HOST memory (n_picks of them; the list must stay the same
+ *                        for all chunks of a stream). */
+#define HPN_SAMPLE_FRACTION 1u
+#define HPN_SAMPLE_PICKS 2u
+typedef struct hpn_sample_rule {
+    uint32_t mode;          /* HPN_SAMPLE_FRACTION or HPN_SAMPLE_PICKS */
+    uint32_t fasta;         /* 0: FASTQ records, 1: FASTA records */
+    uint32_t seed_add;      /* fraction rule */
+    uint32_t threshold;     /* fraction rule: 0 .. 2^24 (2^24 keeps every record) */
+    const uint64_t *picks;  /* pick rule */
+    uint64_t n_picks;
+    uint64_t first_ordinal; /* 0-based ordinal of the STREAM's first record: 0, or where the stream this one continues ended */
+} hpn_sample_rule;
+typedef struct hpn_sample_info {
+    uint64_t n_records;   /* records framed in this chunk */
+    uint64_t n_kept;      /* ... of which kept */
+    uint64_t n_bytes;     /* bytes written to out_text */
+    uint64_t carry_bytes; /* tail bytes kept for the next chunk */
+    uint32_t irregular;   /* HPN_TEXT_* reasons, 0 = chunk processed */
+    uint32_t reserved;
+} hpn_sample_info;
+/* Same chunk contract as hpn_fastq_text_trim (chunks cut anywhere, the unfinished record is carried on the device, `text` and
+ * `out_text` host or device pointers, `last` closes the stream).  Irregular text -- NUL byte, line of 1023+ characters, stream
+ * ending inside a record, HPN_TEXT_DENSE -- is reported in info->irregular and nothing of the chunk is written; a quality line
+ * of another length than the sequence line is regular here (HPN_TEXT_RAGGED / HPN_TEXT_STALE are never raised: whole lines are
+ * copied).  kept_ordinals (host or device pointer, or NULL): receives the 0-based ordinals of the kept records in order --
+ * the pick list for the mate file (-2), whose records are written exactly when the first file's are.
+ * Capacities: a kept record outgrows its input by at most 21 bytes ('_' and up to 20 digits), one more where the input's third
+ * line is empty, one more for FASTA's '>': out_cap = nbytes + 8192 + 23 * (records in the chunk) always suffices, and so does
+ * kept_cap = (nbytes + 8192) / 4.  What does not fit is HPN_E_CAPACITY: nothing is written and the stream is closed. */
+int hpn_fastq_text_sample(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, const hpn_sample_rule *rule,
+                          void *out_text, uint64_t out_cap, uint64_t *kept_ordinals, uint64_t kept_cap, hpn_sample_info *info);
 
 /* ---- ONE text stream framed by several contexts (one per GPU): pieces ----------------------------
  * Record-block sharding of a single FASTQ input (the reference's parallelism stops at
