@@ -88,6 +88,7 @@ class BamRecord:
     mtid: int = -1
     mpos: int = -1
     isize: int = 0
+    aux: bytes = b""  # auxiliary fields as they lie on disk (SAM spec §4.2.4), behind the qualities
 
     def encode(self) -> bytes:
         l_seq = 0 if self.seq == "*" else len(self.seq)
@@ -102,7 +103,7 @@ class BamRecord:
             l_seq, self.mtid, self.mpos, self.isize,
         )
         body += name + struct.pack("<%dI" % len(self.cigar), *self.cigar)
-        body += pack_seq(self.seq) + qual
+        body += pack_seq(self.seq) + qual + self.aux
         return struct.pack("<i", len(body)) + body
 
 

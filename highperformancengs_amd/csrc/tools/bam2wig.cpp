@@ -142,6 +142,8 @@ int main(int argc, char *argv[])
         }
         fclose(wig);
         fclose(chrSize);
+        if (getenv("HPN_TIMING"))   // (which ingest ran: tests assert the device route on files it must take)
+            fprintf(stderr, "[hpn] %s ingest%s\n", bam.on_gpu() ? "GPU" : "host", redo ? "  (abandoned: not decodable on the GPU)" : "");
         if (!redo) break;
       }
       fprintf(stderr, "Converted %s to wig format at %.3f s\n", infiles[i], (double)(usec() - begin) / CLOCKS_PER_SEC);

@@ -7,6 +7,7 @@ reference's outputs are committed as data; no reference source is stored.
 
     python tests/golden/make_golden.py              # everything below
     python tests/golden/make_golden.py c4_synth     # tests/golden/c4_synth/ only
+    python tests/golden/make_golden.py layouts      # bam/layouts.bam and its cases only (the manifest's other cases kept)
 
 Layout written:
     tests/golden/fastq/*            small FASTQ inputs (plain / gzip)
@@ -193,6 +194,123 @@ def make_bam_inputs():
     bamio.write_bam(f"{BAM}/wrap.bam", refs, recs)
 
 
+LAYOUT_REFS = [("chrM", 16569), ("chr1", 400_000), ("chr2", 120_000), ("chrE", 5000)]   # chrE stays empty
+
+
+def _aux_field(rnd, typ, size):
+    """one SAM aux field (SAM spec 4.2.4) of type typ: A c C s S i I f Z H, or B + subtype"""
+    import struct
+    tag = bytes([rnd.randrange(65, 91), rnd.randrange(48, 58)])
+    if typ in ("A", "c", "C", "s", "S", "i", "I", "f"):
+        f = {"A": "c", "c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}[typ]
+        v = {"A": bytes([rnd.randrange(33, 127)]), "c": rnd.randrange(-128, 128), "C": rnd.randrange(256), "s": rnd.randrange(-32768, 32768),
+             "S": rnd.randrange(65536), "i": rnd.randrange(-2 ** 31, 2 ** 31), "I": rnd.randrange(2 ** 32), "f": rnd.uniform(-1e3, 1e3)}[typ]
+        return tag + typ.encode() + struct.pack("<" + f, v)
+    if typ == "Z":
+        return tag + b"Z" + bytes(rnd.randrange(32, 127) for _ in range(size)) + b"\0"
+    if typ == "H":
+        return tag + b"H" + bytes(rnd.choice(b"0123456789ABCDEF") for _ in range(2 * (size // 2))) + b"\0"
+    sub = typ[1]
+    width = {"c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}[sub]
+    n = size // width
+    vals = bytes(rnd.randrange(256) for _ in range(n * width)) if sub != "f" else struct.pack("<%df" % n, *(rnd.uniform(-1, 1) for _ in range(n)))
+    return tag + b"B" + sub.encode() + struct.pack("<i", n) + vals
+
+
+AUX_TYPES = ["A", "c", "C", "s", "S", "i", "I", "f", "Z", "H", "Bc", "BC", "Bs", "BS", "Bi", "BI", "Bf"]
+
+
+def make_layouts_bam():
+    """bam/layouts.bam: the record layouts of real BAM files on the tools' device route -- aux fields of every type (B arrays up to
+    9 kB), read names of 1 .. 254 characters, CIGARs of up to 1,001 operations (M I D N = X), N of 2,047 .. 10^5, SEQ * records, and
+    three 100M69900S all-G reads on chrM whose G/C (70,000) wraps in bam_sliding_count's unsigned short current_GC.  Every M block
+    ends inside its contig but one overhang of 90 bases (shorter than every window size of the cases)."""
+    rnd = random.Random(1515)
+    recs = []
+    names = "".join(chr(c) for c in range(33, 127) if c != 64) * 4
+
+    def name(i):
+        ln = 1 + (i * 37) % 254
+        return names[i % 90:i % 90 + ln]
+
+    def aux(i):
+        if i % 11 == 0:
+            return b""
+        if i % 97 == 5:                                          # MM/ML-like arrays of kilobytes
+            return _aux_field(rnd, "BC", rnd.randrange(2000, 9000)) + _aux_field(rnd, "Z", rnd.randrange(100, 2000))
+        return b"".join(_aux_field(rnd, AUX_TYPES[(i + k) % len(AUX_TYPES)], rnd.randrange(0, 24)) for k in range(1 + i % 6))
+
+    def seq(n, gc=None):
+        return "".join(rnd.choice("ACGTN" if rnd.random() < .05 else "ACGT") for _ in range(n)) if gc is None else gc * n
+
+    def long_cigar(n_ops):
+        ops = []
+        for k in range(n_ops):
+            ops.append("%d%s" % (rnd.randrange(1, 6), "M" if k % 2 == 0 else rnd.choice("IDN=X")))
+        if n_ops % 2 == 0:
+            ops.append("3M")
+        return "".join(ops)
+
+    cigars = ["150M", "40M2I108M", "60M5D90M", "10S140M", "50M2047N100M", "50M2048N100M", "50M2049N100M", "75M10000N75M",
+              "30M100000N120M", "20M3I20M4D107M", "50=50X50M", "5H140M5S"]
+    i = 0
+    for tid, (_, tlen) in enumerate(LAYOUT_REFS[:3]):
+        n = {0: 200, 1: 900, 2: 400}[tid]
+        for p in sorted(rnd.randrange(0, tlen - 250) for _ in range(n)):
+            if tid == 0:
+                cg = "150M"
+            elif i % 53 == 7:
+                cg = long_cigar(rnd.choice([16, 255, 1001]))
+            else:
+                cg = rnd.choice(cigars)
+            cig = bamio.parse_cigar(cg)
+            if p + bamio.cigar_ref_len(cig) > tlen:
+                cig, cg = bamio.parse_cigar("150M"), "150M"
+            ql = sum(c >> 4 for c in cig if (c & 0xF) in (0, 1, 4, 7, 8))
+            s = "*" if i % 13 == 4 else seq(ql)
+            recs.append(bamio.BamRecord(tid=tid, pos=p, flag=rnd.choice([0, 16, 0, 16, 4, 256, 1024, 99, 147]), cigar=cig, seq=s,
+                                        qual=bytes(rnd.randrange(2, 42) for _ in range(ql)) if s != "*" and i % 3 else b"",
+                                        name=name(i), aux=aux(i)))
+            i += 1
+    for p in (100, 150, 16_000):                                 # 100M69900S, all G: per-read G/C 70,000
+        recs.append(bamio.BamRecord(tid=0, pos=p, flag=0, cigar=bamio.parse_cigar("100M69900S"), seq=seq(70_000, "G"),
+                                    name=name(i), aux=aux(i)))
+        i += 1
+    recs.sort(key=lambda r: (r.tid, r.pos))
+    recs.append(bamio.BamRecord(tid=2, pos=LAYOUT_REFS[2][1] - 10, flag=0, cigar=bamio.parse_cigar("100M"), seq=seq(100),
+                                name="over", aux=aux(3)))
+    recs.append(bamio.BamRecord(tid=-1, pos=-1, flag=4, cigar=[], seq="ACGTA", name=name(i), aux=aux(i + 1)))
+    for r in recs:                                               # the domain of the cases (and of the reference)
+        if r.tid >= 0 and r.name != "over":
+            assert r.pos + bamio.cigar_ref_len(r.cigar) <= LAYOUT_REFS[r.tid][1]
+    bamio.write_bam(f"{BAM}/layouts.bam", LAYOUT_REFS, recs, level=6)
+    size = os.path.getsize(f"{BAM}/layouts.bam")
+    print(f"layouts.bam: {len(recs)} records, {size} bytes")
+    assert size <= 512 << 10
+
+
+LAYOUT_CASES = [("depth_layouts", "bam2depth", ["-w", "20000", "-W", "-o", "l", "layouts.bam"]),
+                ("depth_layouts_w1000", "bam2depth", ["-w", "1000", "-W", "-o", "l", "layouts.bam"]),
+                ("wig_layouts", "bam2wig", ["-w", "20000", "-o", "w", "layouts.bam"]),
+                ("wig_layouts_w1000", "bam2wig", ["-w", "1000", "-o", "w", "layouts.bam"]),
+                ("sliding_layouts", "bam_sliding_count", ["-w", "20000", "-o", "s", "layouts.bam"]),
+                ("sliding_layouts_w1000", "bam_sliding_count", ["-w", "1000", "-o", "s", "layouts.bam"])]
+
+
+def layouts():
+    """bam/layouts.bam and LAYOUT_CASES, recorded into the manifest next to the cases already there"""
+    make_layouts_bam()
+    for name, tool, args in LAYOUT_CASES:
+        run_case(name, tool, args, [os.path.join(BAM, "layouts.bam")], gz_over=256 << 10)
+    path = os.path.join(HERE, "manifest.json")
+    with open(path) as f:
+        m = json.load(f)
+    mine = {c["name"] for c in CASES}
+    m["cases"] = [c for c in m["cases"] if c["name"] not in mine] + CASES
+    with open(path, "w") as f:
+        json.dump(m, f, indent=1)
+
+
 CASES = []
 
 C4 = os.path.join(HERE, "c4_synth")
@@ -227,7 +345,7 @@ def make_c4_synth():
         print(f"c4_synth/{case}: {sorted(os.listdir(out_dir))}")
 
 
-def run_case(name, tool, args, inputs, cwd_outputs=True, stdin=None, unordered=False):
+def run_case(name, tool, args, inputs, cwd_outputs=True, stdin=None, unordered=False, gz_over=1 << 20):
     """Run a reference tool in a scratch dir holding copies of `inputs`.
     stdin: a file whose bytes are piped in (the tools read "-" from stdin, IO_stream.h:122-136);
     unordered: stdout rows come in thread completion order (fastq_count.c:126 prints under a mutex): compare as a sorted set."""
@@ -247,7 +365,7 @@ def run_case(name, tool, args, inputs, cwd_outputs=True, stdin=None, unordered=F
         # bam_sliding_count also plots <bam>_hits.png (draw_hits, libgd): not part of the scan path, not recorded
         files = sorted(f for f in set(os.listdir(td)) - before if not f.endswith("_hits.png"))
         for f in files:
-            if os.path.getsize(os.path.join(td, f)) > (1 << 20):   # large reports are stored gzip-compressed
+            if os.path.getsize(os.path.join(td, f)) > gz_over:     # large reports are stored gzip-compressed
                 with open(os.path.join(td, f), "rb") as fh:
                     gz(os.path.join(out_dir, f + ".gz"), fh.read(), 9)
             else:
@@ -332,6 +450,9 @@ def main():
     run_case("sliding_two_files_rev", "bam_sliding_count", ["-w", "5000", "-o", "two", "rand.bam", "e.bam"],
              [bm("rand.bam"), bm("e.bam")])
     run_case("sliding_wrap", "bam_sliding_count", ["-w", "3", "-o", "wr", "wrap.bam"], [bm("wrap.bam")])
+    make_layouts_bam()
+    for name, tool, args in LAYOUT_CASES:
+        run_case(name, tool, args, [bm("layouts.bam")], gz_over=256 << 10)
     # ---- the command-line surface: stdin, a missing input, -h, an unknown option, no arguments, -t over several files ----
     run_case("count_stdin", "fastq_count", ["-H", "-L", "-"], [], stdin=fq("t.fq"))
     run_case("count_stdin_gz", "fastq_count", ["-"], [], stdin=fq("syn_100.fq.gz"))            # gzdopen(0): gzip on stdin too
@@ -373,5 +494,7 @@ def main():
 if __name__ == "__main__":
     if sys.argv[1:] == ["c4_synth"]:   # only tests/golden/c4_synth/
         make_c4_synth()
+    elif sys.argv[1:] == ["layouts"]:
+        layouts()
     else:
         main()

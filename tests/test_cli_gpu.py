@@ -27,6 +27,9 @@ CASES = ["count_a1", "count_a1_gz", "count_empty", "count_nonl", "count_crlf", "
          "wig_a3", "wig_a3_w7", "wig_rand", "wig_rand_w1000", "wig_rand_w37",
          "sliding_a3", "sliding_rand", "sliding_rand_w700", "sliding_rand_w37", "sliding_region", "sliding_region_chr",
          "sliding_two_files", "sliding_two_files_rev", "sliding_wrap",
+         # aux fields of every type, names of 1 .. 254 characters, CIGARs of up to 1,001 operations, 70,000-base reads (records larger
+         # than HPN_BAM_CHUNK=65600's launch): the record layouts of real BAM files on every route
+         "depth_layouts", "depth_layouts_w1000", "wig_layouts", "wig_layouts_w1000", "sliding_layouts", "sliding_layouts_w1000",
          # the command-line surface: stdin ("-", IO_stream.h:122-136), a missing input (O_CREAT makes it, :127), -h / unknown
          # option / no arguments (usage on stderr, exit 1: fastq_count.c:135-156,194-196), -v -z ignored (fastq_trim.c:133-138), five files on
          # three threads (rows in completion order: compared as a sorted set), bam2depth -r running into -s (bam2depth.c:281-285)
@@ -286,6 +289,34 @@ def test_packed_bam_on_several_workers(tmp_path):
                     assert b"[hpn] GPU ingest on 2 workers\n" in p.stderr, p.stderr.decode()
                 for f in outs:
                     assert open(d / f, "rb").read() == expected(case, f), (tool, f, block, env)
+
+
+LAYOUT_CASES = [c for c in CASES if "_layouts" in c]
+
+
+@pytest.mark.parametrize("block", [None, 777, 20000], ids=["samtools", "packed777", "packed20000"])
+@pytest.mark.parametrize("env", [{}, {"HPN_BAM_CHUNK": "65600", "HPN_BAM_ROUNDS": "1"}, {"HPN_NGPU": "3"}],
+                         ids=["default", "chunk64k-rounds1", "3workers"])
+def test_layouts_take_the_device_route(manifest, block, env, tmp_path):
+    """bam/layouts.bam as samtools wrote it and packed htsjdk's way (bamio.repack_bam): every layouts case gives the reference's
+    bytes, and the device ingest really ran -- a fall-back to the host reader would give the same bytes and hide a raw-route bug.
+    HPN_BAM_CHUNK=65600 is smaller than the file's 70,000-base records: one record outgrows a launch."""
+    for case in LAYOUT_CASES:
+        c = manifest[case]
+        d = tmp_path / case
+        d.mkdir()
+        src = os.path.join(GOLDEN, c["inputs"][0])
+        if block is None:
+            shutil.copy(src, d)
+            shutil.copy(src + ".bai", d)
+        else:
+            bamio.repack_bam(src, str(d / os.path.basename(src)), block, level=1)
+        p = subprocess.run([os.path.join(BIN, c["tool"])] + c["args"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           env={**os.environ, "HPN_TIMING": "1", **env})
+        assert p.returncode == c["returncode"], p.stderr.decode()
+        assert b"GPU ingest" in p.stderr and b"abandoned" not in p.stderr and b"host ingest" not in p.stderr, (case, p.stderr.decode())
+        for f in c["files"]:
+            assert open(d / f, "rb").read() == expected(case, f), (case, f)
 
 
 def test_region_reads_from_the_index_offset(tmp_path):

@@ -150,7 +150,8 @@ def test_trim_soa_matches_stream_on_wellformed():
 
 @pytest.mark.parametrize("case,bam,W", [("depth_a3", "e.bam", 100), ("depth_a3_wig", "e.bam", 100),
                                         ("depth_rand", "rand.bam", 20000),
-                                        ("depth_rand_w1000", "rand.bam", 1000)])
+                                        ("depth_rand_w1000", "rand.bam", 1000), ("depth_layouts", "layouts.bam", 20000),
+                                        ("depth_layouts_w1000", "layouts.bam", 1000)])
 def test_bam2depth_text(manifest, case, bam, W):
     soa = bamio.read_bam_records(BAM(bam))
     bed, depth, wig, chrom = orc.bam2depth_text(soa, W)
@@ -186,7 +187,8 @@ def test_bam2depth_stdout_and_second_file(manifest):
 
 @pytest.mark.parametrize("case,bam,W,n", [("wig_a3", "e.bam", 100, 1), ("wig_a3_w7", "e.bam", 7, 1),
                                           ("wig_rand", "rand.bam", 20000, 1), ("wig_rand_w1000", "rand.bam", 1000, 1),
-                                          ("wig_rand_w37", "e.bam", 37, 1), ("wig_rand_w37", "rand.bam", 37, 2)])
+                                          ("wig_rand_w37", "e.bam", 37, 1), ("wig_rand_w37", "rand.bam", 37, 2),
+                                          ("wig_layouts", "layouts.bam", 20000, 1), ("wig_layouts_w1000", "layouts.bam", 1000, 1)])
 def test_bam2wig_text(case, bam, W, n):
     soa = bamio.read_bam_records(BAM(bam))
     wig, chrom = orc.bam2wig_text(soa, W)
@@ -202,7 +204,35 @@ SLIDING = [("sliding_a3", "e.bam", 100, "s.txt"), ("sliding_rand", "rand.bam", 2
            ("sliding_rand_w700", "rand.bam", 700, "s.txt"), ("sliding_rand_w37", "rand.bam", 37, "s.txt"),
            ("sliding_two_files", "e.bam", 500, "two.txt"),          # only the first input file is reported
            ("sliding_two_files_rev", "rand.bam", 5000, "two.txt"),
-           ("sliding_wrap", "wrap.bam", 3, "wr.txt")]               # 66,667 windows: the unsigned-short index wraps
+           ("sliding_wrap", "wrap.bam", 3, "wr.txt"),               # 66,667 windows: the unsigned-short index wraps
+           ("sliding_layouts", "layouts.bam", 20000, "s.txt"), ("sliding_layouts_w1000", "layouts.bam", 1000, "s.txt")]
+
+
+def test_layouts_bam_is_in_the_cases_domain():
+    """bam/layouts.bam (aux fields, long names and CIGARs, 70,000-base all-G reads): every M block ends inside its contig but one
+    overhang shorter than every window size of its cases, no window's G/C sum reaches 2^24, and chrM's first window holds the
+    wrapped per-read G/C of the three all-G reads (3 x (70,000 mod 65,536) = 13,392) -- what the recorded reports rest on."""
+    soa = bamio.read_bam_records(BAM("layouts.bam"))
+    over = []
+    for r in range(len(soa.tid)):
+        if soa.tid[r] < 0:
+            continue
+        q, end = int(soa.pos[r]), 0
+        for c in soa.cigar[soa.cigar_off[r]:soa.cigar_off[r + 1]]:
+            op, ln = int(c) & 0xF, int(c) >> 4
+            if op in (0, 2, 3):
+                q += ln
+                end = q if op == 0 else end
+        if end > soa.refs[soa.tid[r]][1]:
+            over.append(end - soa.refs[soa.tid[r]][1])
+    assert len(over) == 1 and over[0] < 1000
+    assert max(np.diff(soa.cigar_off.astype(np.int64))) >= 1000 and max(len(n) for n in soa.names) >= 250
+    for W in (1000, 20000):
+        rc, off, bins, gc, *_ = orc.window_counts(soa, W)
+        assert rc == 0 and int(gc.max()) < 1 << 24
+    rc, off, bins, gc, *_ = orc.window_counts(soa, 1000)
+    allg = (soa.l_qseq == 70_000) & (soa.tid == 0)
+    assert allg.sum() == 3 and int(gc[0]) >= 2 * (70_000 - 65_536)
 
 
 @pytest.mark.parametrize("case,bam,W,out", SLIDING)
