@@ -50,12 +50,26 @@ class SampleInfo(C.Structure):
 SAMPLE_FRACTION, SAMPLE_PICKS = 1, 2
 
 
+class UniqInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class UniqResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_unique", C.c_uint64), ("hash_size", C.c_uint64), ("unmatched", C.c_int64),
+                ("out_bytes", C.c_uint64 * 2), ("hash_clashes", C.c_uint64), ("unmatched_name", C.c_char * 1024)]
+
+
+UNIQ_TABLE_ORDER, UNIQ_KEY_ORDER = 0, 1
+
+
 class TextPiece(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 TEXT_PIECE_TAIL = 4096
 TEXT_NUL, TEXT_LONG_LINE, TEXT_RAGGED, TEXT_PARTIAL, TEXT_LEN, TEXT_DENSE, TEXT_STALE = 1, 2, 4, 8, 16, 32, 64
+TEXT_SHORT_QUAL = 128
+TEXT_INPLACE_PAD = 8192
 
 
 class Rqc(C.Structure):
@@ -126,6 +140,11 @@ SYMBOLS = [
     ("hpn_fastq_text_records", _int, [_vp, _vp, _u64, _int, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_trim", _int, [_vp, _vp, _u64, _int, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_sample", _int, [_vp, _vp, _u64, _int, C.POINTER(SampleRule), _vp, _u64, _vp, _u64, C.POINTER(SampleInfo)]),
+    ("hpn_fastq_uniq_begin", _int, [_vp, _int, _u64, _u32]),
+    ("hpn_fastq_uniq_add", _int, [_vp, _int, _vp, _u64, _int, C.POINTER(UniqInfo)]),
+    ("hpn_fastq_uniq_finish", _int, [_vp, C.POINTER(UniqResult)]),
+    ("hpn_fastq_uniq_write", _int, [_vp, _int, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_sort_pairs_u64", _int, [_vp, _vp, _vp, _u64]),
     ("hpn_fastq_text_piece_lines", _int, [_vp, _vp, _u64, _u32, _u64, _int, C.POINTER(TextPiece)]),
     ("hpn_fastq_text_piece_count", _int, [_vp, _u64, _u32, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_piece_trim", _int, [_vp, _u64, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
@@ -187,7 +206,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 2:
+    if L.hpn_abi_version() != 3:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -249,6 +249,41 @@ class Context:
             return b"", kept[:0], info
         return out[:int(info.n_bytes)].tobytes(), kept[:int(info.n_kept)].copy(), info
 
+    # ---- duplicate removal (gzfastq_uniq) ------------------------------------------------
+    def uniq_begin(self, paired=False, max_bytes=0, hash_bits=0):
+        self._ck(self.L.hpn_fastq_uniq_begin(self.h, int(bool(paired)), int(max_bytes), int(hash_bits)), "hpn_fastq_uniq_begin")
+
+    def uniq_add(self, chunk, mate=0, last=False):
+        """One chunk of FASTQ text of one mate into the session's device store; returns the hpn_uniq_info."""
+        chunk, n = self._text(chunk)
+        info = _lib.UniqInfo()
+        self._ck(self.L.hpn_fastq_uniq_add(self.h, int(mate), _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_fastq_uniq_add")
+        return info
+
+    def uniq_finish(self):
+        res = _lib.UniqResult()
+        self._ck(self.L.hpn_fastq_uniq_finish(self.h, C.byref(res)), "hpn_fastq_uniq_finish")
+        return res
+
+    def uniq_output(self, which=_lib.UNIQ_TABLE_ORDER, mate=0, slice_bytes=1 << 24):
+        """The whole text of one output, fetched in slices (hpn_fastq_uniq_write)."""
+        parts, at = [], 0
+        buf = np.zeros(max(int(slice_bytes), 1), np.uint8)
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_fastq_uniq_write(self.h, int(which), int(mate), at, _ptr(buf), buf.size, C.byref(got)), "hpn_fastq_uniq_write")
+            if not got.value:
+                return b"".join(parts)
+            parts.append(buf[:got.value].tobytes())
+            at += got.value
+
+    def sort_pairs(self, keys, vals):
+        """Stable ascending sort of uint64 keys with their uint32 payload on the device (hpn_sort_pairs_u64); returns copies."""
+        keys, vals = np.array(keys, np.uint64), np.array(vals, np.uint32)
+        assert keys.shape == vals.shape and keys.ndim == 1
+        self._ck(self.L.hpn_sort_pairs_u64(self.h, _ptr(keys) if keys.size else None, _ptr(vals) if keys.size else None, keys.size), "hpn_sort_pairs_u64")
+        return keys, vals
+
     # ---- one stream framed by several contexts: pieces ---------------------------------
     def text_piece_lines(self, text, head, own_bytes, last=False):
         """First half of a piece (hpn_fastq_text_piece_lines): text = head byte + piece + tail; returns hpn_text_piece."""

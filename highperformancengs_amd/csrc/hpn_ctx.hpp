@@ -10,6 +10,7 @@
 #include "hpngs.h"
 
 struct hpn_ctx;
+struct hpn_uniq_state;   // hpn_uniq.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -89,6 +90,7 @@ struct hpn_ctx {
     uint32_t gz_n_chunks = 0, gz_sym_cap = 0;
     uint64_t r_n = 0;
     bool r_fields = false;  // the SoA view of the current index has been gathered
+    hpn_uniq_state *uq = nullptr;   // hpn_fastq_uniq_*: the store, the descriptors, the sorts' arrays
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -114,6 +116,8 @@ inline int fail(hpn_ctx *c, int status, const char *fmt, ...)
             return hpn::fail((c), HPN_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
                              __FILE__, __LINE__);                                             \
     } while (0)
+
+void uniq_release(hpn_ctx *c);   // hpn_uniq.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

@@ -39,6 +39,7 @@ using namespace hpn;
 namespace {
 
 constexpr uint32_t kCarryCap = 8192;  // room in front of a chunk for the unfinished record of the previous one
+static_assert(kCarryCap == HPN_TEXT_INPLACE_PAD, "hpngs.h promises callers of the in-place route this many bytes");
 constexpr int kStateWords = 16;       // kernels/fastq_text.hip: kTs*
 enum { kTsLines = 0, kTsRecs, kTsFlags, kTsUnterminated, kTsConsumed, kTsTotalLo, kTsTotalHi, kTsErr, kTsTicket1, kTsTicket2, kTsOwnLines, kTsKept };
 

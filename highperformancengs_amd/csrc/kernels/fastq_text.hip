@@ -7,7 +7,7 @@
 // pure function of the newline positions, and these kernels compute it on the
 // device from the raw bytes:
 //
-//   k_text_lines    newline index: every workgroup counts the '\n' of its 64 KiB
+//   k_text_lines    newline index: every workgroup counts the '\n' of its 128 KiB
 //                   tile (SWAR on dwordx4 loads), one decoupled look-back chain
 //                   (scan.hpp) turns the counts into global line numbers, and the
 //                   position of line j's '\n' lands in nl[j].
@@ -149,7 +149,7 @@ __device__ __forceinline__ void line_masks(const uint8_t *__restrict__ slot, uin
 // positions < own_end are also counted into kTsOwnLines -- what this piece adds to the stream's
 // line count, and how many record starts it can own; 0: not a piece.
 //
-// A tile is 64 KiB, a wave's part of it 16 contiguous KiB: load k of a wave covers 1 KiB.  Newlines are numbered
+// A tile is 128 KiB (kTxtTile), a wave's part of it 16 contiguous KiB: load k of a wave covers 1 KiB.  Newlines are numbered
 // in (wave, load, lane, bit) order = by position.  Inside a wave: the counts of two loads share one DPP prefix sum
 // (16 bits each: at most 17 per lane), eight of them before the look-back, so that what stays live across the
 // look-back is 16 masks + 8 packed offsets (the first form of this kernel held 256 VGPRs: two waves per SIMD).

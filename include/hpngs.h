@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 2
+#define HPN_ABI_VERSION 3
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -224,6 +224,10 @@ typedef struct hpn_text_info {
 #define HPN_TEXT_DENSE 32u     /* more than one line per 4 bytes: not worth indexing */
 #define HPN_TEXT_STALE 64u     /* trim: S beyond a read's end (the reference copies what the record's
                                   earlier lines left in its buffer; the host framer reproduces that) */
+#define HPN_TEXT_SHORT_QUAL 128u /* uniq: quality line two or more bytes shorter than the sequence (the reference sums
+                                  bytes outside its buffer) */
+/* The writable bytes hpn_fastq_text_count_inplace needs in front of the text it frames where it lies. */
+#define HPN_TEXT_INPLACE_PAD 8192u
 
 int hpn_fastq_text_begin(hpn_ctx *ctx);
 /* count_read's loop: adds into the context's device accumulators exactly like
@@ -231,7 +235,7 @@ int hpn_fastq_text_begin(hpn_ctx *ctx);
 int hpn_fastq_text_count(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, uint32_t tally_flags,
                          hpn_text_info *info);
 /* The same for text that lies on the device already (a batch inflated there: hpn_gz_inflate_dev, hpn_bgzf_inflate_dev),
- * framed WHERE IT LIES: d_text must have 8192 writable bytes of device memory in front of it (the carried bytes of the
+ * framed WHERE IT LIES: d_text must have HPN_TEXT_INPLACE_PAD writable bytes of device memory in front of it (the carried bytes of the
  * chunk before are laid there) and 64 readable bytes behind d_text + nbytes; nothing else is copied.  The text may be
  * overwritten as soon as the call returns.  Chunks framed in place and chunks framed by hpn_fastq_text_count may follow each
  * other in one stream. */
@@ -288,6 +292,62 @@ typedef struct hpn_sample_info {
  * kept_cap = (nbytes + 8192) / 4.  What does not fit is HPN_E_CAPACITY: nothing is written and the stream is closed. */
 int hpn_fastq_text_sample(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, const hpn_sample_rule *rule,
                           void *out_text, uint64_t out_cap, uint64_t *kept_ordinals, uint64_t kept_cap, hpn_sample_info *info);
+
+/* ---- gzfastq_uniq.c: one record per distinct sequence ------------------------------------------------
+ * The reads of one stream (or the pairs of two) are collapsed by their sequence (pairs: by both sequences joined, so
+ * "AC" + "G" and "A" + "CG" are one key).  Per key: the number of records, and as representative the EARLIEST record
+ * whose quality sum (the first seq_len bytes of the quality string, both mates added) is the greatest.  Records are
+ * framed as readNextNode frames them (gzfastq_uniq.c:170-192): name, sequence and quality are their lines without the
+ * last byte -- a '\r' stays, a last line without '\n' loses a real character; a lone line without '\n' behind the
+ * last record is no record.  An output record is "name\tcount\nsequence\n+\nquality\n".
+ *
+ *   hpn_fastq_uniq_begin   opens a session (closing the context's earlier one).  `paired`: two streams, mate 0 and 1.
+ *                          max_bytes: the most text (both mates, as fed) the device store may hold; 0 = half of the
+ *                          device memory that is free now, the other half being the reserve for the store's growth and
+ *                          the sorts' arrays.  hash_bits: 0 = records are grouped by all 64 bits of the grouping hash;
+ *                          1 .. 63 keeps only that many -- a verification aid: the outputs must not depend on it,
+ *                          because keys are always compared by their bytes.
+ *   hpn_fastq_uniq_add     one chunk of mate `mate` (the chunk contract of hpn_fastq_text_sample: cut anywhere, host or
+ *                          device pointer, `last` closes the mate's stream; the mates may be fed in any interleaving).
+ *                          Irregular text -- HPN_TEXT_NUL, _LONG_LINE, _PARTIAL, _DENSE, _SHORT_QUAL -- is reported in
+ *                          info->irregular and closes the session.  A chunk with which the store would outgrow max_bytes:
+ *                          HPN_E_CAPACITY (the message tells how much was needed), session closed.  2^31 or more
+ *                          records: HPN_E_DOMAIN.
+ *   hpn_fastq_uniq_finish  after every mate's last chunk: groups, orders, fills *result.  Pairs: reading stops at the
+ *                          first ordinal whose mate is missing (mate 0 has more records) or whose names differ within
+ *                          the bytes in front of name 0's first space (no space: the names must be equal);
+ *                          result->unmatched is that ordinal (-1: none), unmatched_name the name of mate 0 there, and
+ *                          n_records counts the pairs in front of it.
+ *   hpn_fastq_uniq_write   copies up to `cap` bytes of an output, from byte `offset` on, to `out` (host or device).
+ *                          HPN_UNIQ_TABLE_ORDER: the order in which the reference walks its hash table (mate 0, and
+ *                          mate 1 of a paired session; result->out_bytes[mate] bytes).  HPN_UNIQ_KEY_ORDER: single-end
+ *                          only, keys ascending by memcmp, then length (out_bytes[0] bytes as well).  Reading one
+ *                          output front to back before the next one costs one formatting pass per output. */
+typedef struct hpn_uniq_info {
+    uint64_t n_records;   /* records framed by this call */
+    uint64_t store_bytes; /* text held by the store (both mates) after this call */
+    uint32_t irregular;   /* HPN_TEXT_* reasons, 0 = chunk processed */
+    uint32_t reserved;
+} hpn_uniq_info;
+typedef struct hpn_uniq_result {
+    uint64_t n_records;    /* records (pairs) that were keyed */
+    uint64_t n_unique;     /* distinct keys */
+    uint64_t hash_size;    /* the size the reference's table would have ("hash size: ") */
+    int64_t unmatched;     /* pairs: the first ordinal without a matching mate, else -1 */
+    uint64_t out_bytes[2]; /* bytes of the outputs of mate 0 and mate 1 */
+    uint64_t hash_clashes; /* records whose grouping hash equalled their neighbour's over different bytes */
+    char unmatched_name[1024];
+} hpn_uniq_result;
+#define HPN_UNIQ_TABLE_ORDER 0
+#define HPN_UNIQ_KEY_ORDER 1
+int hpn_fastq_uniq_begin(hpn_ctx *ctx, int paired, uint64_t max_bytes, uint32_t hash_bits);
+int hpn_fastq_uniq_add(hpn_ctx *ctx, int mate, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info);
+int hpn_fastq_uniq_finish(hpn_ctx *ctx, hpn_uniq_result *result);
+int hpn_fastq_uniq_write(hpn_ctx *ctx, int which_output, int mate, uint64_t offset, void *out, uint64_t cap,
+                         uint64_t *written);
+/* The stable radix sort behind it on its own: n < 2^31 pairs, ascending by key, equal keys in their given order.
+ * keys and vals: host or device pointers, sorted in place. */
+int hpn_sort_pairs_u64(hpn_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n);
 
 /* ---- ONE text stream framed by several contexts (one per GPU): pieces ----------------------------
  * Record-block sharding of a single FASTQ input (the reference's parallelism stops at
