@@ -62,6 +62,14 @@ class UniqResult(C.Structure):
 UNIQ_TABLE_ORDER, UNIQ_KEY_ORDER = 0, 1
 
 
+class SortInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SortResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64), ("refined", C.c_uint64), ("rounds", C.c_uint32), ("lone_line", C.c_uint32)]
+
+
 class TextPiece(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -145,6 +153,10 @@ SYMBOLS = [
     ("hpn_fastq_uniq_finish", _int, [_vp, C.POINTER(UniqResult)]),
     ("hpn_fastq_uniq_write", _int, [_vp, _int, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_sort_pairs_u64", _int, [_vp, _vp, _vp, _u64]),
+    ("hpn_fastq_sort_begin", _int, [_vp, _int, _u64]),
+    ("hpn_fastq_sort_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
+    ("hpn_fastq_sort_finish", _int, [_vp, C.POINTER(SortResult)]),
+    ("hpn_fastq_sort_write", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_fastq_text_piece_lines", _int, [_vp, _vp, _u64, _u32, _u64, _int, C.POINTER(TextPiece)]),
     ("hpn_fastq_text_piece_count", _int, [_vp, _u64, _u32, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_piece_trim", _int, [_vp, _u64, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
@@ -206,7 +218,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 3:
+    if L.hpn_abi_version() != 4:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

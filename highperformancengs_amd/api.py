@@ -277,6 +277,34 @@ class Context:
             parts.append(buf[:got.value].tobytes())
             at += got.value
 
+    # ---- the whole file ordered by name or sequence (gzfastq_sort) ---------------------------
+    def sort_begin(self, by_name=False, max_bytes=0):
+        self._ck(self.L.hpn_fastq_sort_begin(self.h, int(bool(by_name)), int(max_bytes)), "hpn_fastq_sort_begin")
+
+    def sort_add(self, chunk, last=False):
+        """One chunk of FASTQ text into the session's device store; returns the hpn_sort_info."""
+        chunk, n = self._text(chunk)
+        info = _lib.SortInfo()
+        self._ck(self.L.hpn_fastq_sort_add(self.h, _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_fastq_sort_add")
+        return info
+
+    def sort_finish(self):
+        res = _lib.SortResult()
+        self._ck(self.L.hpn_fastq_sort_finish(self.h, C.byref(res)), "hpn_fastq_sort_finish")
+        return res
+
+    def sort_output(self, slice_bytes=1 << 24):
+        """The whole sorted text, fetched in slices (hpn_fastq_sort_write)."""
+        parts, at = [], 0
+        buf = np.zeros(max(int(slice_bytes), 1), np.uint8)
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_fastq_sort_write(self.h, at, _ptr(buf), buf.size, C.byref(got)), "hpn_fastq_sort_write")
+            if not got.value:
+                return b"".join(parts)
+            parts.append(buf[:got.value].tobytes())
+            at += got.value
+
     def sort_pairs(self, keys, vals):
         """Stable ascending sort of uint64 keys with their uint32 payload on the device (hpn_sort_pairs_u64); returns copies."""
         keys, vals = np.array(keys, np.uint64), np.array(vals, np.uint32)

@@ -11,6 +11,7 @@
 
 struct hpn_ctx;
 struct hpn_uniq_state;   // hpn_uniq.hip
+struct hpn_sort_state;   // hpn_sort.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -91,6 +92,7 @@ struct hpn_ctx {
     uint64_t r_n = 0;
     bool r_fields = false;  // the SoA view of the current index has been gathered
     hpn_uniq_state *uq = nullptr;   // hpn_fastq_uniq_*: the store, the descriptors, the sorts' arrays
+    hpn_sort_state *sq = nullptr;   // hpn_fastq_sort_*: the same for the whole-file sort
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -118,6 +120,7 @@ inline int fail(hpn_ctx *c, int status, const char *fmt, ...)
     } while (0)
 
 void uniq_release(hpn_ctx *c);   // hpn_uniq.hip
+void sort_release(hpn_ctx *c);   // hpn_sort.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

@@ -511,4 +511,32 @@ hipError_t uniq_sort_pairs(uint64_t *d_keys, uint32_t *d_vals, uint32_t n, int b
     return radix_sort_pairs(d_keys, d_vals, n, begin_bit, end_bit, ws, st);
 }
 
+// radix_sort_pairs over the digits of `digits` only (bit d: the key bits [8 d, 8 d + 8) take part), lowest first: stable, in
+// place, one copy back when the number of passes is odd.
+hipError_t uniq_sort_pairs_digits(uint64_t *d_keys, uint32_t *d_vals, uint32_t n, uint32_t digits, uint64_t *d_keys_tmp, uint32_t *d_vals_tmp,
+                             uint32_t *d_hist, uint32_t *d_offs, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t s)
+{
+    if (n < 2 || !(digits & 255u)) return hipSuccess;
+    const uint32_t tiles = sort_tiles(n);
+    const unsigned grid = (tiles + kSortThreads / kWave - 1) / (kSortThreads / kWave);
+    const size_t hw = (size_t)256 * tiles;
+    uint64_t *ka = d_keys, *kb = d_keys_tmp;
+    uint32_t *va = d_vals, *vb = d_vals_tmp;
+    for (int d = 0; d < 8; ++d) {
+        if (!((digits >> d) & 1u)) continue;
+        hipLaunchKernelGGL(k_radix_hist, dim3(grid), dim3(kSortThreads), 0, s, ka, n, 8 * d, tiles, d_hist);
+        hipError_t e = launch_excl_scan<uint32_t, uint32_t>(d_hist, d_offs, hw, d_status, d_ticket, d_err, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_radix_scatter, dim3(grid), dim3(kSortThreads), 0, s, ka, va, n, 8 * d, tiles, d_offs, kb, vb);
+        std::swap(ka, kb);
+        std::swap(va, vb);
+    }
+    if (ka != d_keys) {
+        hipError_t e = hipMemcpyAsync(d_keys, ka, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(d_vals, va, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace hpn

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 3
+#define HPN_ABI_VERSION 4
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -348,6 +348,44 @@ int hpn_fastq_uniq_write(hpn_ctx *ctx, int which_output, int mate, uint64_t offs
 /* The stable radix sort behind it on its own: n < 2^31 pairs, ascending by key, equal keys in their given order.
  * keys and vals: host or device pointers, sorted in place. */
 int hpn_sort_pairs_u64(hpn_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n);
+
+/* ---- gzfastq_sort.c: the whole file ordered by name or by sequence ---------------------------------------
+ * The records of one stream, framed as readNextNode frames them (see above), in ascending order of their KEY LINE -- the
+ * whole name line with its '@' and comment (by_name) or the sequence line: first by its length, then by its bytes compared as
+ * unsigned; records with equal keys stay in input order (the reference's qsort is glibc's merge sort).  An output record is
+ * "name\nsequence\n+\nquality\n".
+ *
+ *   hpn_fastq_sort_begin   opens a session (closing the context's earlier one).  max_bytes: as for hpn_fastq_uniq_begin.
+ *   hpn_fastq_sort_add     one chunk (the chunk contract of hpn_fastq_uniq_add: cut anywhere, host or device pointer, `last`
+ *                          closes the stream).  Irregular text -- HPN_TEXT_NUL, _LONG_LINE, _PARTIAL, _DENSE -- is reported in
+ *                          info->irregular and closes the session; a quality line shorter than its sequence is regular here
+ *                          (nothing reads it against the sequence).  HPN_E_CAPACITY and HPN_E_DOMAIN (2^31 or more records)
+ *                          as there.
+ *   hpn_fastq_sort_finish  after the last chunk: orders the records, formats the output on the device, fills *result.
+ *                          The order is built most significant bytes first: round 0 sorts all records by length and their
+ *                          first 6 bytes, round k >= 1 only the records of runs that are still undecided, by their next 8
+ *                          bytes.  result->rounds counts the rounds (round 0 included; 0 without records),
+ *                          result->refined the records that rounds 1, 2, ... worked on, added up.
+ *   hpn_fastq_sort_write   copies up to `cap` bytes of the output (result->out_bytes in all), from byte `offset` on, to `out`
+ *                          (host or device). */
+typedef struct hpn_sort_info {
+    uint64_t n_records;   /* records framed by this call */
+    uint64_t store_bytes; /* text held by the store after this call */
+    uint32_t irregular;   /* HPN_TEXT_* reasons, 0 = chunk processed */
+    uint32_t reserved;
+} hpn_sort_info;
+typedef struct hpn_sort_result {
+    uint64_t n_records; /* records ordered */
+    uint64_t out_bytes; /* bytes of the output */
+    uint64_t refined;   /* sum over the rounds k >= 1 of the records they sorted */
+    uint32_t rounds;    /* rounds run, round 0 included */
+    uint32_t lone_line; /* 1: a line without '\n' stands behind the last record -- no record (gzeof is true after its gzgets),
+                           but the reference's count_read counts it */
+} hpn_sort_result;
+int hpn_fastq_sort_begin(hpn_ctx *ctx, int by_name, uint64_t max_bytes);
+int hpn_fastq_sort_add(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
+int hpn_fastq_sort_finish(hpn_ctx *ctx, hpn_sort_result *result);
+int hpn_fastq_sort_write(hpn_ctx *ctx, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
 
 /* ---- ONE text stream framed by several contexts (one per GPU): pieces ----------------------------
  * Record-block sharding of a single FASTQ input (the reference's parallelism stops at
