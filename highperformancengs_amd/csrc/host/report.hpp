@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "cpus.hpp"
 #include "hpngs.h"
 
 namespace hpn {
@@ -296,6 +297,18 @@ inline void die_hpn(hpn_ctx *ctx, int rc, const char *what)
 {
     fprintf(stderr, "%s: %s (%s)\n", what, hpn_strerror(rc), ctx ? hpn_ctx_last_error(ctx) : "");
     leave(2);
+}
+
+// The context of a tool that works on ONE device: HPN_DEVICE's (default 0), the process bound next to it (host/cpus.hpp).
+inline hpn_ctx *open_tool_ctx()
+{
+    hpn_ctx *ctx = nullptr;
+    int dev0 = 0;
+    if (const char *d = getenv("HPN_DEVICE")) dev0 = atoi(d);
+    const int rc = hpn_ctx_create(dev0, &ctx);
+    if (rc != HPN_OK) die_hpn(nullptr, rc, "hpn_ctx_create");
+    bind_for_device(ctx);
+    return ctx;
 }
 
 }  // namespace hpn

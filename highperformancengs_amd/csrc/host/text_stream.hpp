@@ -23,6 +23,7 @@
 
 #include "fastq_reader.hpp"
 #include "hpngs.h"
+#include "report.hpp"
 
 namespace hpn {
 
@@ -40,6 +41,14 @@ inline size_t text_chunk_bytes()
     if (v >= 64) return (size_t)v;
     const size_t c = ((size_t)32 << 20) / (size_t)text_workers_in_flight();
     return c < ((size_t)4 << 20) ? (size_t)4 << 20 : c;
+}
+
+// device text goes to the framer (and a device output to its file) in slices of this many bytes (HPN_TEXT_SLICE: tests cut small
+// texts into several)
+inline uint64_t text_slice_bytes(uint64_t by_default)
+{
+    const char *e = test_env("HPN_TEXT_SLICE");
+    return !e ? by_default : (uint64_t)atoll(e) < 64 ? 64 : (uint64_t)atoll(e);
 }
 
 // How many of the `requested` workers (-t) to start.  gzip input is inflate-bound at a few
@@ -414,5 +423,37 @@ private:
     std::condition_variable cv_;
     std::thread th_;
 };
+
+// An output text of `total` bytes that lies on the device into the file prefix + suffix (fcreat_outfile's rule), `slice` bytes at
+// a time: fetch(at, buf, cap, &got) copies the bytes from `at` on into a pinned buffer (and dies itself where the ABI refuses);
+// the writer's thread puts one slice into the file while the next one is fetched.
+template <class Fetch>
+void write_device_output(hpn_ctx *ctx, const char *tool, const char *prefix, const char *suffix, uint64_t total, uint64_t slice, Fetch fetch)
+{
+    FILE *out = fcreat_outfile(prefix, suffix);
+    if (!out) leave(2);
+    {
+        AsyncWriter w(ctx, out, slice);
+        if (!w.ok()) die_hpn(ctx, HPN_E_NOMEM, tool);
+        for (uint64_t at = 0; at < total;) {
+            int idx;
+            void *buf = w.acquire(&idx);
+            uint64_t got = 0;
+            fetch(at, buf, slice, &got);
+            w.submit(idx, got);
+            if (!got) break;
+            at += got;
+        }
+        w.finish();
+        if (w.failed()) {
+            fprintf(stderr, "%s: writing %s%s failed (%s)\n", tool, prefix, suffix, errno ? strerror(errno) : "short write");
+            leave(2);
+        }
+    }
+    if (fclose(out) != 0) {
+        fprintf(stderr, "%s: writing %s%s failed (%s)\n", tool, prefix, suffix, strerror(errno));
+        leave(2);
+    }
+}
 
 }  // namespace hpn

@@ -128,28 +128,11 @@ int main(int argc, char *argv[])
         if (usable) done = true;
         else start_over();
     }
-    // a plain .fastq.gz (one member): block starts found here, the stretches inflated on the GPU (host/gz_gpu.hpp)
-    // Writing the trimmed text is as slow as the host's own two-pass inflate on 16 cores (1.1 s vs 1.25 s on 3 GB), so
-    // this route is taken when the host has few cores (or when asked for: HPN_GZ_GPU=1)
-    const char *want_gz_gpu = getenv("HPN_GZ_GPU");
-    const bool gz_on_gpu = gz_gpu_enabled() && (usable_cpus() <= 8 || (want_gz_gpu && want_gz_gpu[0] == '1') || test_env("HPN_GZ_GPU_FORCE"));
-    if (!done && !exact && to_file && from_file && gz_on_gpu && !test_env("HPN_NO_MGZ") && !test_env("HPN_NO_PGZ") &&
-        is_plain_gzip_file(infile)) {
+    // a plain .fastq.gz (one member): block starts found here, the stretches inflated on the GPU (host/gz_gpu.hpp: when
+    // the route is taken -- gz_gpu_route_wanted -- and how the stream is sized for a tool that writes text)
+    if (!done && !exact && to_file && from_file && gz_gpu_route_wanted() && is_plain_gzip_file(infile)) {
         GzGpuStream gs;
-        const long cpus = usable_cpus();
-        uint32_t per_call = 5120;
-        (void)hpn_inflate_slots(ctx, &per_call);                          // stretches the chip decodes at once
-        const uint32_t slots = per_call;
-        if (const char *e = test_env("HPN_GZ_BATCH")) per_call = (uint32_t)atol(e);
-        // several device calls per file, so that the writer thread has text to write while the next part is inflated:
-        // a quarter of the file per call, in stretches small enough to fill the chip each time
-        size_t stretch = 0;
-        struct stat sb;
-        if (!test_env("HPN_GZ_STRETCH") && stat(infile, &sb) == 0) {
-            stretch = ((size_t)sb.st_size / 4 / slots + 65536) & ~(size_t)65535;
-            stretch = stretch < ((size_t)256 << 10) ? (size_t)256 << 10 : stretch > ((size_t)1 << 20) ? (size_t)1 << 20 : stretch;
-        }
-        bool usable = gs.open(ctx, infile, (int)(cpus < 1 ? 1 : cpus > 16 ? 16 : cpus), per_call < 1 ? 1 : per_call, stretch);
+        bool usable = open_gz_gpu_stream(gs, ctx, infile);
         if (usable) {
             AsyncWriter writer(ctx, out, ocap);
             if (!writer.ok()) die_hpn(ctx, HPN_E_NOMEM, "fastq_trim");

@@ -22,13 +22,10 @@
 #include <algorithm>
 #include <string>
 
-#include "../host/bam_gpu.hpp"
 #include "../host/fastq_reader.hpp"
-#include "../host/gz_gpu.hpp"
 #include "../host/gz_writer.hpp"
-#include "../host/tally_stream.hpp"
-#include "../host/text_stream.hpp"
 #include "../host/report.hpp"
+#include "../host/text_feed.hpp"
 
 using namespace hpn;
 
@@ -106,6 +103,12 @@ static std::vector<uint64_t> draw_picks(uint64_t n, uint64_t pick)
     return xs;
 }
 
+[[noreturn]] static void write_failed()
+{
+    fprintf(stderr, "gzfastq_sample: writing the output failed (%s)\n", errno ? strerror(errno) : "short write");
+    leave(2);
+}
+
 struct Pass {
     const hpn_sample_rule *rule = nullptr;   // nullptr: count_read -- records are counted, nothing is written
     GzWriter *out = nullptr;
@@ -113,8 +116,7 @@ struct Pass {
     uint64_t n_records = 0, n_kept = 0;
 };
 
-// One pass over `path` on the device, through the routes fastq_trim takes.  false: the text is not regular (or a route
-// gave up half way) -- nothing of this pass counts and the caller frames the file on the host.
+// One pass over a file on the device: the sink of feed_fastq_file (host/text_feed.hpp).
 class DevicePass {
 public:
     DevicePass(hpn_ctx *ctx, Pass &p) : ctx_(ctx), p_(p) {}
@@ -123,75 +125,7 @@ public:
         if (obuf_) hpn_host_free(ctx_, obuf_);
     }
 
-    bool run(const char *path)
-    {
-        if (bam_gpu_enabled() && !test_env("HPN_NO_BGZF") && is_bgzf_file(path)) {   // bgzip: the blocks are inflated on the GPU
-            BgzfGpuStream gs;
-            bool usable = gs.open_text(ctx_, path);
-            if (usable) {
-                begin();
-                for (bool fin = false; usable && !fin;) {
-                    hpn_raw_info bi;
-                    const int r = gs.next(&bi);
-                    if (r < 0) {
-                        usable = false;
-                        break;
-                    }
-                    fin = r == 0 || gs.at_eof();
-                    if (!device_text(gs.d_raw(), r == 0 ? 0 : bi.n_records, fin)) return false;
-                }
-            }
-            if (usable) return true;
-            if (!start_over()) return false;
-        }
-        const char *want = getenv("HPN_GZ_GPU");
-        const bool gz_on_gpu = gz_gpu_enabled() && (usable_cpus() <= 8 || (want && want[0] == '1') || test_env("HPN_GZ_GPU_FORCE"));
-        if (gz_on_gpu && !test_env("HPN_NO_MGZ") && !test_env("HPN_NO_PGZ") && is_plain_gzip_file(path)) {   // gzip members inflated on the GPU in stretches
-            GzGpuStream gs;
-            const long cpus = usable_cpus();
-            uint32_t per_call = 5120;
-            (void)hpn_inflate_slots(ctx_, &per_call);
-            const uint32_t slots = per_call;
-            if (const char *e = test_env("HPN_GZ_BATCH")) per_call = (uint32_t)atol(e);
-            size_t stretch = 0;
-            struct stat sb;
-            if (!test_env("HPN_GZ_STRETCH") && stat(path, &sb) == 0) {
-                stretch = ((size_t)sb.st_size / 4 / slots + 65536) & ~(size_t)65535;
-                stretch = stretch < ((size_t)256 << 10) ? (size_t)256 << 10 : stretch > ((size_t)1 << 20) ? (size_t)1 << 20 : stretch;
-            }
-            bool usable = gs.open(ctx_, path, (int)(cpus < 1 ? 1 : cpus > 16 ? 16 : cpus), per_call < 1 ? 1 : per_call, stretch);
-            if (usable) {
-                begin();
-                for (bool fin = false; usable && !fin;) {
-                    uint64_t n = 0;
-                    const int r = gs.next(&n);
-                    if (r < 0) {
-                        usable = false;
-                        break;
-                    }
-                    fin = r == 0 || gs.at_end();
-                    if (!device_text(gs.d_text(), n, fin)) return false;
-                }
-            }
-            if (usable) return true;
-            if (!start_over()) return false;
-        }
-        // text read (and, where compressed, inflated) by the host's reader threads, framed on the device
-        TextPump pump(ctx_, path, text_chunk_bytes());
-        if (!pump.ok()) die_hpn(ctx_, HPN_E_NOMEM, "gzfastq_sample");
-        begin();
-        TextPump::Chunk c;
-        while (pump.next(c)) {
-            const bool ok = chunk(c.p, c.n, c.eof);
-            pump.recycle(c);
-            if (!ok) return false;
-        }
-        if (pump.damaged()) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-        return true;
-    }
-
-private:
-    void begin()
+    void route_begins()
     {
         const int rc = hpn_fastq_text_begin(ctx_);
         if (rc != HPN_OK) die_hpn(ctx_, rc, "gzfastq_sample");
@@ -201,19 +135,6 @@ private:
         p_.n_records = p_.n_kept = 0;
         if (p_.kept) p_.kept->clear();
         return !p_.out || p_.out->restart();
-    }
-    // text on the device, in slices (each framed by one call)
-    bool device_text(const uint8_t *d_text, uint64_t total, bool fin)
-    {
-        uint64_t slice = (uint64_t)32 << 20;
-        if (const char *e = test_env("HPN_TEXT_SLICE")) slice = (uint64_t)atoll(e) < 64 ? 64 : (uint64_t)atoll(e);
-        for (uint64_t at = 0; at < total || (fin && total == 0);) {
-            const uint64_t k = total - at < slice ? total - at : slice;
-            if (!chunk(d_text + at, k, fin && at + k == total)) return false;
-            at += k;
-            if (total == 0) break;
-        }
-        return true;
     }
     // one chunk through the ABI; false: irregular text (or a sample that outgrew the buffer: records of a few bytes)
     bool chunk(const void *text, uint64_t n, bool last)
@@ -245,11 +166,8 @@ private:
         if (!p_.out->write(obuf_, si.n_bytes)) write_failed();
         return true;
     }
-    [[noreturn]] static void write_failed()
-    {
-        fprintf(stderr, "gzfastq_sample: writing the output failed (%s)\n", errno ? strerror(errno) : "short write");
-        leave(2);
-    }
+
+private:
     hpn_ctx *ctx_;
     Pass &p_;
     void *obuf_ = nullptr;
@@ -317,12 +235,15 @@ static void host_pass(const char *path, Pass &p)
 
 static void run_pass(hpn_ctx *ctx, const char *path, Pass &p)
 {
-    bool done = false;
+    // kIrregular: the text is not regular (or a route gave up half way and the output could not be rewound) -- nothing of the
+    // pass counts and the file is framed on the host
+    FeedEnd end = FeedEnd::kIrregular;
     if (text_path_enabled()) {
         DevicePass d(ctx, p);
-        done = d.run(path);
+        end = feed_fastq_file(ctx, path, "gzfastq_sample", d);
     }
-    if (!done) host_pass(path, p);
+    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+    if (end == FeedEnd::kIrregular) host_pass(path, p);
 }
 
 static std::string out_name(const char *in, const char *mid)
@@ -339,12 +260,6 @@ static GzWriter *create_out(const std::string &name)
         leave(2);
     }
     return w;
-}
-
-[[noreturn]] static void write_failed()
-{
-    fprintf(stderr, "gzfastq_sample: writing the output failed (%s)\n", errno ? strerror(errno) : "short write");
-    leave(2);
 }
 
 int main(int argc, char *argv[])
@@ -387,12 +302,7 @@ int main(int argc, char *argv[])
             fprintf(stderr, "open file %s failed\n", f);
             return 2;
         }
-    hpn_ctx *ctx = nullptr;
-    int dev0 = 0;
-    if (const char *d = getenv("HPN_DEVICE")) dev0 = atoi(d);
-    int rc = hpn_ctx_create(dev0, &ctx);
-    if (rc != HPN_OK) die_hpn(nullptr, rc, "hpn_ctx_create");
-    bind_for_device(ctx);
+    hpn_ctx *ctx = open_tool_ctx();
     const long long begin = usec();
     double t_deflate = 0, t_waited = 0;
     int gz_threads = 0;

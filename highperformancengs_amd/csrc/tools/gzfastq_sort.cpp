@@ -18,12 +18,9 @@
 
 #include <string>
 
-#include "../host/bam_gpu.hpp"
 #include "../host/fastq_reader.hpp"
-#include "../host/gz_gpu.hpp"
-#include "../host/tally_stream.hpp"
-#include "../host/text_stream.hpp"
 #include "../host/report.hpp"
+#include "../host/text_feed.hpp"
 
 using namespace hpn;
 
@@ -64,13 +61,6 @@ static unsigned long parse_reads_num(const char *str)
     return v;
 }
 
-static uint64_t slice_bytes()
-{
-    uint64_t slice = (uint64_t)32 << 20;
-    if (const char *e = test_env("HPN_TEXT_SLICE")) slice = (uint64_t)atoll(e) < 64 ? 64 : (uint64_t)atoll(e);
-    return slice;
-}
-
 static bool add_chunk(hpn_ctx *ctx, const void *text, uint64_t n, bool last, uint64_t *records)
 {
     hpn_sort_info si;
@@ -84,82 +74,24 @@ static bool add_chunk(hpn_ctx *ctx, const void *text, uint64_t n, bool last, uin
     return si.irregular == 0;
 }
 
-// A file into the session on the device, through the routes gzfastq_uniq takes.  false: the text is not regular (or a route
-// gave up half way) -- the session is void and the caller frames the file on the host.
-class DeviceFeed {
-public:
-    DeviceFeed(hpn_ctx *ctx, uint64_t *records) : ctx_(ctx), records_(records) {}
-
-    bool run(const char *path)
-    {
-        if (bam_gpu_enabled() && !test_env("HPN_NO_BGZF") && is_bgzf_file(path)) {   // bgzip: the blocks are inflated on the GPU
-            BgzfGpuStream gs;
-            if (gs.open_text(ctx_, path)) {
-                for (bool fin = false; !fin;) {
-                    hpn_raw_info bi;
-                    const int r = gs.next(&bi);
-                    if (r < 0) return false;
-                    fin = r == 0 || gs.at_eof();
-                    if (!device_text(gs.d_raw(), r == 0 ? 0 : bi.n_records, fin)) return false;
-                }
-                return true;
-            }
-        }
-        const char *want = getenv("HPN_GZ_GPU");
-        const bool gz_on_gpu = gz_gpu_enabled() && (usable_cpus() <= 8 || (want && want[0] == '1') || test_env("HPN_GZ_GPU_FORCE"));
-        if (gz_on_gpu && !test_env("HPN_NO_MGZ") && !test_env("HPN_NO_PGZ") && is_plain_gzip_file(path)) {   // gzip members inflated on the GPU in stretches
-            GzGpuStream gs;
-            const long cpus = usable_cpus();
-            uint32_t per_call = 5120;
-            (void)hpn_inflate_slots(ctx_, &per_call);
-            const uint32_t slots = per_call;
-            if (const char *e = test_env("HPN_GZ_BATCH")) per_call = (uint32_t)atol(e);
-            size_t stretch = 0;
-            struct stat sb;
-            if (!test_env("HPN_GZ_STRETCH") && stat(path, &sb) == 0) {
-                stretch = ((size_t)sb.st_size / 4 / slots + 65536) & ~(size_t)65535;
-                stretch = stretch < ((size_t)256 << 10) ? (size_t)256 << 10 : stretch > ((size_t)1 << 20) ? (size_t)1 << 20 : stretch;
-            }
-            if (gs.open(ctx_, path, (int)(cpus < 1 ? 1 : cpus > 16 ? 16 : cpus), per_call < 1 ? 1 : per_call, stretch)) {
-                for (bool fin = false; !fin;) {
-                    uint64_t n = 0;
-                    const int r = gs.next(&n);
-                    if (r < 0) return false;
-                    fin = r == 0 || gs.at_end();
-                    if (!device_text(gs.d_text(), n, fin)) return false;
-                }
-                return true;
-            }
-        }
-        // text read (and, where compressed, inflated) by the host's reader threads, framed on the device
-        TextPump pump(ctx_, path, text_chunk_bytes());
-        if (!pump.ok()) die_hpn(ctx_, HPN_E_NOMEM, "gzfastq_sort");
-        TextPump::Chunk c;
-        while (pump.next(c)) {
-            const bool ok = add_chunk(ctx_, c.p, c.n, c.eof, records_);
-            pump.recycle(c);
-            if (!ok) return false;
-        }
-        if (pump.damaged()) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-        return true;
-    }
-
-private:
-    // text on the device, in slices (each framed by one call)
-    bool device_text(const uint8_t *d_text, uint64_t total, bool fin)
-    {
-        const uint64_t slice = slice_bytes();
-        for (uint64_t at = 0; at < total || (fin && total == 0);) {
-            const uint64_t k = total - at < slice ? total - at : slice;
-            if (!add_chunk(ctx_, d_text + at, k, fin && at + k == total, records_)) return false;
-            at += k;
-            if (total == 0) break;
-        }
-        return true;
-    }
-    hpn_ctx *ctx_;
-    uint64_t *records_;
+// The file's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
+struct FileSink {
+    hpn_ctx *ctx;
+    uint64_t *records;
+    void route_begins() {}
+    bool start_over() { return false; }   // the session is void: the caller begins a new one
+    bool chunk(const void *text, uint64_t n, bool last) { return add_chunk(ctx, text, n, last, records); }
 };
+
+// A file into the session on the device.  false: the text is not regular (or a route gave up half way) -- the session is void
+// and the caller frames the file on the host.
+static bool device_feed(hpn_ctx *ctx, const char *path, uint64_t *records)
+{
+    FileSink sink{ctx, records};
+    const FeedEnd end = feed_fastq_file(ctx, path, "gzfastq_sort", sink);
+    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+    return end == FeedEnd::kDone;
+}
 
 // the whole inflated stream in memory (standard input, which cannot be read twice; a file whose text is not regular)
 static void slurp(const char *path, std::string &mem)
@@ -247,36 +179,6 @@ static void host_feed(hpn_ctx *ctx, const char *path, const std::string &mem, ui
     if (!add_chunk(ctx, text.data(), text.size(), true, records)) refuse(path, "records too short for the device's line index");
 }
 
-static void write_output(hpn_ctx *ctx, uint64_t total, const char *prefix, const char *suffix)
-{
-    FILE *out = fcreat_outfile(prefix, suffix);
-    if (!out) leave(2);
-    const uint64_t slice = slice_bytes();
-    {
-        AsyncWriter w(ctx, out, slice);   // the writer's thread puts one slice into the file while the next one is fetched
-        if (!w.ok()) die_hpn(ctx, HPN_E_NOMEM, "gzfastq_sort");
-        for (uint64_t at = 0; at < total;) {
-            int idx;
-            void *buf = w.acquire(&idx);
-            uint64_t got = 0;
-            const int rc = hpn_fastq_sort_write(ctx, at, buf, slice, &got);
-            if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_sort_write");
-            w.submit(idx, got);
-            if (!got) break;
-            at += got;
-        }
-        w.finish();
-        if (w.failed()) {
-            fprintf(stderr, "gzfastq_sort: writing %s%s failed (%s)\n", prefix, suffix, errno ? strerror(errno) : "short write");
-            leave(2);
-        }
-    }
-    if (fclose(out) != 0) {
-        fprintf(stderr, "gzfastq_sort: writing %s%s failed (%s)\n", prefix, suffix, strerror(errno));
-        leave(2);
-    }
-}
-
 int main(int argc, char *argv[])
 {
     bind_before_runtime();
@@ -300,12 +202,8 @@ int main(int argc, char *argv[])
     if (!by_name && !by_seq) by_seq = 1;
     const bool is_stdin = strncmp(infile, "-", 1) == 0 || !strcmp(infile, "");
     const bool rewindable = !is_stdin || lseek(STDIN_FILENO, 0, SEEK_CUR) != (off_t)-1;   // (gzrewind on a pipe fails)
-    hpn_ctx *ctx = nullptr;
-    int dev0 = 0;
-    if (const char *d = getenv("HPN_DEVICE")) dev0 = atoi(d);
-    int rc = hpn_ctx_create(dev0, &ctx);
-    if (rc != HPN_OK) die_hpn(nullptr, rc, "hpn_ctx_create");
-    bind_for_device(ctx);
+    hpn_ctx *ctx = open_tool_ctx();
+    int rc;
     const long long begin = usec();
 
     std::string mem;
@@ -328,8 +226,7 @@ int main(int argc, char *argv[])
                 at += k;
             } while (done && at < mem.size());
         } else {
-            DeviceFeed feed(ctx, &records);
-            done = feed.run(infile);
+            done = device_feed(ctx, infile, &records);
         }
     }
     if (!done) {
@@ -356,7 +253,11 @@ int main(int argc, char *argv[])
     fprintf(stderr, "done read file at %.3f s\n", (double)(fed - begin) / CLOCKS_PER_SEC);
     const long long ordered = usec();
     fprintf(stderr, "done qsort file at %.3f s\n", (double)(ordered - begin) / CLOCKS_PER_SEC);
-    write_output(ctx, res.out_bytes, outfile, by_name ? "_sort_by_name.fq" : "_sort_by_seq.fq");
+    write_device_output(ctx, "gzfastq_sort", outfile, by_name ? "_sort_by_name.fq" : "_sort_by_seq.fq", res.out_bytes, text_slice_bytes((uint64_t)32 << 20),
+                        [&](uint64_t at, void *buf, uint64_t cap, uint64_t *got) {
+                            const int wrc = hpn_fastq_sort_write(ctx, at, buf, cap, got);
+                            if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_fastq_sort_write");
+                        });
     if (getenv("HPN_TIMING"))
         fprintf(stderr, "[hpn] sort: reading and framing %.3f s, ordering and formatting %.3f s, writing %.3f s; %u rounds, %llu records refined\n",
                 (double)(fed - begin) / 1e6, (double)(ordered - fed) / 1e6, (double)(usec() - ordered) / 1e6, res.rounds, (unsigned long long)res.refined);

@@ -20,12 +20,9 @@
 
 #include <string>
 
-#include "../host/bam_gpu.hpp"
 #include "../host/fastq_reader.hpp"
-#include "../host/gz_gpu.hpp"
-#include "../host/tally_stream.hpp"
-#include "../host/text_stream.hpp"
 #include "../host/report.hpp"
+#include "../host/text_feed.hpp"
 
 using namespace hpn;
 
@@ -51,100 +48,34 @@ static void usage(const char *prog)
     leave(2);
 }
 
-static uint64_t slice_bytes()
-{
-    uint64_t slice = (uint64_t)32 << 20;
-    if (const char *e = test_env("HPN_TEXT_SLICE")) slice = (uint64_t)atoll(e) < 64 ? 64 : (uint64_t)atoll(e);
-    return slice;
-}
-
-// One mate's file into the session on the device, through the routes gzfastq_sample takes.  false: the text is not regular
-// (or a route gave up half way) -- the session is void and the caller frames the files on the host.
-class DeviceFeed {
-public:
-    DeviceFeed(hpn_ctx *ctx, int mate) : ctx_(ctx), mate_(mate) {}
-
-    bool run(const char *path)
-    {
-        if (bam_gpu_enabled() && !test_env("HPN_NO_BGZF") && is_bgzf_file(path)) {   // bgzip: the blocks are inflated on the GPU
-            BgzfGpuStream gs;
-            if (gs.open_text(ctx_, path)) {
-                for (bool fin = false; !fin;) {
-                    hpn_raw_info bi;
-                    const int r = gs.next(&bi);
-                    if (r < 0) return false;
-                    fin = r == 0 || gs.at_eof();
-                    if (!device_text(gs.d_raw(), r == 0 ? 0 : bi.n_records, fin)) return false;
-                }
-                return true;
-            }
-        }
-        const char *want = getenv("HPN_GZ_GPU");
-        const bool gz_on_gpu = gz_gpu_enabled() && (usable_cpus() <= 8 || (want && want[0] == '1') || test_env("HPN_GZ_GPU_FORCE"));
-        if (gz_on_gpu && !test_env("HPN_NO_MGZ") && !test_env("HPN_NO_PGZ") && is_plain_gzip_file(path)) {   // gzip members inflated on the GPU in stretches
-            GzGpuStream gs;
-            const long cpus = usable_cpus();
-            uint32_t per_call = 5120;
-            (void)hpn_inflate_slots(ctx_, &per_call);
-            const uint32_t slots = per_call;
-            if (const char *e = test_env("HPN_GZ_BATCH")) per_call = (uint32_t)atol(e);
-            size_t stretch = 0;
-            struct stat sb;
-            if (!test_env("HPN_GZ_STRETCH") && stat(path, &sb) == 0) {
-                stretch = ((size_t)sb.st_size / 4 / slots + 65536) & ~(size_t)65535;
-                stretch = stretch < ((size_t)256 << 10) ? (size_t)256 << 10 : stretch > ((size_t)1 << 20) ? (size_t)1 << 20 : stretch;
-            }
-            if (gs.open(ctx_, path, (int)(cpus < 1 ? 1 : cpus > 16 ? 16 : cpus), per_call < 1 ? 1 : per_call, stretch)) {
-                for (bool fin = false; !fin;) {
-                    uint64_t n = 0;
-                    const int r = gs.next(&n);
-                    if (r < 0) return false;
-                    fin = r == 0 || gs.at_end();
-                    if (!device_text(gs.d_text(), n, fin)) return false;
-                }
-                return true;
-            }
-        }
-        // text read (and, where compressed, inflated) by the host's reader threads, framed on the device
-        TextPump pump(ctx_, path, text_chunk_bytes());
-        if (!pump.ok()) die_hpn(ctx_, HPN_E_NOMEM, "gzfastq_uniq");
-        TextPump::Chunk c;
-        while (pump.next(c)) {
-            const bool ok = chunk(c.p, c.n, c.eof);
-            pump.recycle(c);
-            if (!ok) return false;
-        }
-        if (pump.damaged()) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-        return true;
-    }
-
-private:
-    // text on the device, in slices (each framed by one call)
-    bool device_text(const uint8_t *d_text, uint64_t total, bool fin)
-    {
-        const uint64_t slice = slice_bytes();
-        for (uint64_t at = 0; at < total || (fin && total == 0);) {
-            const uint64_t k = total - at < slice ? total - at : slice;
-            if (!chunk(d_text + at, k, fin && at + k == total)) return false;
-            at += k;
-            if (total == 0) break;
-        }
-        return true;
-    }
+// One mate's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
+struct MateSink {
+    hpn_ctx *ctx;
+    int mate;
+    void route_begins() {}
+    bool start_over() { return false; }   // the session is void: the caller begins a new one
     bool chunk(const void *text, uint64_t n, bool last)
     {
         hpn_uniq_info ui;
-        const int rc = hpn_fastq_uniq_add(ctx_, mate_, text, n, last, &ui);
+        const int rc = hpn_fastq_uniq_add(ctx, mate, text, n, last, &ui);
         if (rc == HPN_E_CAPACITY) {
-            fprintf(stderr, "gzfastq_uniq: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx_));
+            fprintf(stderr, "gzfastq_uniq: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
             leave(2);
         }
-        if (rc != HPN_OK) die_hpn(ctx_, rc, "hpn_fastq_uniq_add");
+        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniq_add");
         return ui.irregular == 0;
     }
-    hpn_ctx *ctx_;
-    int mate_;
 };
+
+// One mate's file into the session on the device.  false: the text is not regular (or a route gave up half way) -- the session
+// is void and the caller frames the files on the host.
+static bool device_feed(hpn_ctx *ctx, int mate, const char *path)
+{
+    MateSink sink{ctx, mate};
+    const FeedEnd end = feed_fastq_file(ctx, path, "gzfastq_uniq", sink);
+    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+    return end == FeedEnd::kDone;
+}
 
 // readNextNode (gzfastq_uniq.c:170-192) with the exact gzgets emulation: the gzeof test sits behind the FIRST gzgets only.
 // The record goes out as canonical text -- the fields as strlen sees them, every line closed -- which the device frames like
@@ -224,36 +155,6 @@ static void host_feed(hpn_ctx *ctx, const char *read1, const char *read2, HostEr
     flush(1, t2, true);
 }
 
-static void write_output(hpn_ctx *ctx, int which, int mate, uint64_t total, const char *prefix, const char *suffix)
-{
-    FILE *out = fcreat_outfile(prefix, suffix);
-    if (!out) leave(2);
-    const uint64_t slice = slice_bytes();
-    {
-        AsyncWriter w(ctx, out, slice);
-        if (!w.ok()) die_hpn(ctx, HPN_E_NOMEM, "gzfastq_uniq");
-        for (uint64_t at = 0; at < total;) {
-            int idx;
-            void *buf = w.acquire(&idx);
-            uint64_t got = 0;
-            const int rc = hpn_fastq_uniq_write(ctx, which, mate, at, buf, slice, &got);
-            if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniq_write");
-            w.submit(idx, got);
-            if (!got) break;
-            at += got;
-        }
-        w.finish();
-        if (w.failed()) {
-            fprintf(stderr, "gzfastq_uniq: writing %s%s failed (%s)\n", prefix, suffix, errno ? strerror(errno) : "short write");
-            leave(2);
-        }
-    }
-    if (fclose(out) != 0) {
-        fprintf(stderr, "gzfastq_uniq: writing %s%s failed (%s)\n", prefix, suffix, strerror(errno));
-        leave(2);
-    }
-}
-
 int main(int argc, char *argv[])
 {
     bind_before_runtime();
@@ -283,24 +184,15 @@ int main(int argc, char *argv[])
             fprintf(stderr, "open file %s failed\n", f);
             return 2;
         }
-    hpn_ctx *ctx = nullptr;
-    int dev0 = 0;
-    if (const char *d = getenv("HPN_DEVICE")) dev0 = atoi(d);
-    int rc = hpn_ctx_create(dev0, &ctx);
-    if (rc != HPN_OK) die_hpn(nullptr, rc, "hpn_ctx_create");
-    bind_for_device(ctx);
+    hpn_ctx *ctx = open_tool_ctx();
+    int rc;
     const long long begin = usec();
 
     bool done = false;
     HostError herr;
     if (text_path_enabled()) {
         if ((rc = hpn_fastq_uniq_begin(ctx, read2 != nullptr, 0, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniq_begin");
-        DeviceFeed f1(ctx, 0);
-        done = f1.run(read1);
-        if (done && read2) {
-            DeviceFeed f2(ctx, 1);
-            done = f2.run(read2);
-        }
+        done = device_feed(ctx, 0, read1) && (!read2 || device_feed(ctx, 1, read2));
     }
     if (!done) {
         if ((rc = hpn_fastq_uniq_begin(ctx, read2 != nullptr, 0, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniq_begin");
@@ -316,12 +208,19 @@ int main(int argc, char *argv[])
     fprintf(stderr, "hash size: %ld\n", (long)res.hash_size);
     fprintf(stderr, "Finished load hash at %.3f s\n", (double)(usec() - begin) / CLOCKS_PER_SEC);
     const long long grouped = usec();
+    auto write_output = [&](int which, int mate, const char *suffix) {
+        write_device_output(ctx, "gzfastq_uniq", outfile, suffix, res.out_bytes[mate], text_slice_bytes((uint64_t)32 << 20),
+                            [&](uint64_t at, void *buf, uint64_t cap, uint64_t *got) {
+                                const int wrc = hpn_fastq_uniq_write(ctx, which, mate, at, buf, cap, got);
+                                if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_fastq_uniq_write");
+                            });
+    };
     if (read2) {
-        write_output(ctx, HPN_UNIQ_TABLE_ORDER, 0, res.out_bytes[0], outfile, "_1_uniq.fq");
-        write_output(ctx, HPN_UNIQ_TABLE_ORDER, 1, res.out_bytes[1], outfile, "_2_uniq.fq");
+        write_output(HPN_UNIQ_TABLE_ORDER, 0, "_1_uniq.fq");
+        write_output(HPN_UNIQ_TABLE_ORDER, 1, "_2_uniq.fq");
     } else {
-        write_output(ctx, HPN_UNIQ_TABLE_ORDER, 0, res.out_bytes[0], outfile, "_uniq.fq");
-        write_output(ctx, HPN_UNIQ_KEY_ORDER, 0, res.out_bytes[0], outfile, "_sortKeyUniq.fq");
+        write_output(HPN_UNIQ_TABLE_ORDER, 0, "_uniq.fq");
+        write_output(HPN_UNIQ_KEY_ORDER, 0, "_sortKeyUniq.fq");
     }
     if (getenv("HPN_TIMING"))
         fprintf(stderr, "[hpn] uniq: reading and keying %.3f s, grouping and ordering %.3f s, formatting and writing %.3f s; %llu hash clashes\n",

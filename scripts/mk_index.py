@@ -32,7 +32,7 @@ groups = [
     ("BASELINE configurations at their stated sizes", ["c2_gz_1e9.py", "c4_full.py", "c4_full_show.py", "c4_30x_big.py", "scale8.sh", "scale8.py"]),
     ("Same-session A/B of variant builds",
      ["ab_variant.sh", "ab_inflate.sh", "ab_bgzf.sh", "ab_sweep.sh", "ab_k5.sh", "ab_depth.py", "ab_gz_route.sh", "ab_gz_windows.sh", "ab_k1_sched.sh",
-      "ab_waves.sh", "ab_build.sh"]),
+      "ab_waves.sh", "ab_build.sh", "ab_e2e.py"]),
     ("Soaks and sanitizers (beyond the test suite)",
      ["soak_inflate.py", "soak_inflate_damaged.py", "soak_raw_walk.py", "soak_text_lines.py", "sanitize_host.sh", "sanitize_shard.sh", "emu_raw_chain.py"]),
     ("Inputs and housekeeping", ["bam_synth.cpp", "mk_index.py"]),
