@@ -89,6 +89,8 @@ public:
 
     // zlib refused the stream (a member's CRC-32 / ISIZE / data): what was delivered is NOT what the reference's gzgets hands out
     bool damaged() const { return damaged_; }
+    // members whose gzip header parsed and which the quick decoder (fast_inflate.hpp) gave up on or got wrong: zlib took them
+    unsigned long handed_back() const { return handed_back_.load(); }
 
     // Up to n bytes of the uncompressed stream; fewer only at its end (or at an error, like gzread).
     size_t read(void *dst, size_t n)
@@ -345,6 +347,7 @@ private:
             hist = base - keep;
             cur = base;
         }
+        if (!j->cancel) handed_back_.fetch_add(1);
         if (!published && !j->cancel) return 0;
         std::lock_guard<std::mutex> lk(m_);
         j->st = kFailed;
@@ -532,6 +535,7 @@ private:
     bool stop_ = false;
     gzFile fallback_ = nullptr;
     bool damaged_ = false;
+    std::atomic<unsigned long> handed_back_{0};
 };
 
 }  // namespace hpn

@@ -90,7 +90,7 @@ int hpn_gz_inflate_finish_dev(hpn_ctx *c, const uint8_t *d_window_in, uint8_t *d
     HPN_HIP(c, hipStreamSynchronize(c->stream));
     if (n_bounds && !summary[1]) {   // members that ended inside stretches: where in this call's text, and their ISIZE
         if (n_bounds > kGzBounds) n_bounds = kGzBounds;
-        struct Meta { uint32_t n_out, status, final_block, reserved; uint64_t end_bit, text_off; };
+        struct Meta { uint32_t n_out, status, final_block, reach; uint64_t end_bit, text_off; };
         struct Bound { uint32_t chunk, n_out, isize, crc; };
         std::vector<Meta> metas(n_chunks);
         std::vector<Bound> bounds(n_bounds);
@@ -107,7 +107,7 @@ int hpn_gz_inflate_finish_dev(hpn_ctx *c, const uint8_t *d_window_in, uint8_t *d
     info->n_bytes = summary[0];
     info->status = (uint32_t)summary[1], info->bad_chunk = (uint32_t)summary[2], info->final_chunk = (uint32_t)summary[3];
     if (info->final_chunk) {  // where that stretch stopped: the member's trailer
-        struct { uint32_t n_out, status, final_block, reserved; uint64_t end_bit, text_off; } m;
+        struct { uint32_t n_out, status, final_block, reach; uint64_t end_bit, text_off; } m;
         HPN_HIP(c, hipMemcpyAsync(&m, (const uint8_t *)c->g_meta.p + (size_t)(info->final_chunk - 1) * 32, 32, hipMemcpyDeviceToHost, c->stream));
         HPN_HIP(c, hipStreamSynchronize(c->stream));
         info->end_bit = m.end_bit;

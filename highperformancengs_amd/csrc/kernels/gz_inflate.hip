@@ -38,12 +38,22 @@ struct GzBound {   // a member that ended inside a stretch, and went on with the
     uint32_t isize, crc;      // ISIZE and CRC-32 of its trailer
 };
 struct GzMeta {
-    uint32_t n_out, status, final_block, reserved;
+    uint32_t n_out, status, final_block;
+    uint32_t reach;     // bytes in front of the stretch that its matches refer to (at most kGzHist)
     uint64_t end_bit;   // bit position reached (byte-aligned after a final block), from in_off * 8
     uint64_t text_off;  // filled by k_gz_windows
 };
 
 constexpr uint32_t kGzHist = 32768;
+// A match that reaches in front of the stream's first byte (zlib: "invalid distance too far back"): the stretch cannot know -- what
+// lies in front of it is not its business -- but the walk over the stretches does: `text` bytes of this call in front of the
+// stretch, and a whole window where the caller handed one in (no window: the call starts the stream).  Status 25, found by
+// tests/test_inflate_foreign_gpu.py: such a match read zeros and the call reported success.
+constexpr uint32_t kGzErrBeforeStart = 25;
+__device__ __forceinline__ uint32_t gz_reach_status(const GzMeta &m, unsigned long long text, bool has_window)
+{
+    return !m.status && !has_window && (unsigned long long)m.reach > text ? kGzErrBeforeStart : m.status;
+}
 
 // where the symbols go: 16 bits each, straight to global memory; a match reads its source back from there, or names the
 // byte of the 32 KiB in front of the stretch it would have copied
@@ -51,7 +61,8 @@ struct SymSink {
     static constexpr bool kDry = false;
     uint16_t *out;
     uint32_t out_len, op, safe;   // op: symbols decoded; symbols below `safe` are known to have reached memory
-    __device__ __forceinline__ void pin_state() { op = uni(op), safe = uni(safe); }
+    uint32_t far;                 // how many bytes in front of the stretch its matches reach (0: none), for k_gz_windows' check
+    __device__ __forceinline__ void pin_state() { op = uni(op), safe = uni(safe), far = uni(far); }
     // entry e: [23:16] the literal, [31:24] the second one of a pair.  (Byte offsets in 32 bits: a stretch's symbols stay far
     // below 2 GiB.)
     __device__ __forceinline__ void lits(bool mine, bool two, uint32_t at, uint32_t e)
@@ -74,6 +85,10 @@ struct SymSink {
         if (__builtin_amdgcn_ballot_w64(ask && from >= (int32_t)safe)) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             safe = base;
+        }
+        if (__builtin_amdgcn_ballot_w64(ask && from < 0)) {   // (the stretch's first 32 KiB only: a wave-uniform maximum, in a scalar register)
+            const uint32_t deepest = lane_of(wave_prefix_max(ask && from < 0 ? (uint32_t)-from : 0u), kWave - 1);
+            far = deepest > far ? deepest : far;
         }
         if (ask) val = from < 0 ? 256u + kGzHist + (uint32_t)from : (uint32_t)out[from];
         return val;
@@ -105,7 +120,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(HPN_INF_E
         stage(s, b, in, in_len);
         refill(s, b, in, in_len);
         drop(b, ck.start_bit);
-        SymSink sink{out, out_len, 0u, 0u};
+        SymSink sink{out, out_len, 0u, 0u, 0u};
         uint32_t &op = sink.op;
         uint32_t err = 0;
         bool last = false, arrived = false;
@@ -223,7 +238,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(HPN_INF_E
         if (!err && last && end_bit != ~0ull) err = 22;
         if (lane == 0) {
             GzMeta m;
-            m.n_out = op, m.status = err, m.final_block = last ? 1u : 0u, m.reserved = 0;
+            m.n_out = op, m.status = err, m.final_block = last ? 1u : 0u, m.reach = sink.far;
             m.end_bit = pos, m.text_off = 0;
             meta[ci] = m;
         }
@@ -467,7 +482,7 @@ __global__ __launch_bounds__(kGzWinThreads) void k_gz_windows(const uint16_t *__
 #pragma unroll
         for (int q = 0; q < kPer; ++q) sv[q] = n_chunks ? tail(0, (uint32_t)tid + (uint32_t)q * 1024u) : 0u;
         for (uint32_t k = 0; k < n_chunks; ++k) {
-            const uint32_t n = meta[k].n_out, st = meta[k].status;
+            const uint32_t n = meta[k].n_out, st = gz_reach_status(meta[k], text, window_in != nullptr);
             if (st && !bad) bad = st, bad_at = k;
             if (meta[k].final_block) fin = k + 1u;
             if (tid == 0) meta[k].text_off = text;
@@ -490,7 +505,7 @@ __global__ __launch_bounds__(kGzWinThreads) void k_gz_windows(const uint16_t *__
         }
     } else {
     for (uint32_t k = 0; k < n_chunks; ++k) {
-        const uint32_t n = meta[k].n_out, st = meta[k].status;
+        const uint32_t n = meta[k].n_out, st = gz_reach_status(meta[k], text, window_in != nullptr);
         if (st && !bad) bad = st, bad_at = k;
         if (meta[k].final_block) fin = k + 1u;
         if (tid == 0) meta[k].text_off = text;
@@ -563,7 +578,7 @@ __global__ __launch_bounds__(1024) void k_gz_windows_lds(const uint16_t *__restr
     u64 text = 0;
     uint32_t bad = 0, bad_at = 0, fin = 0;
     for (uint32_t k = 0; k < n_chunks; ++k) {
-        const uint32_t n = meta[k].n_out, st = meta[k].status;
+        const uint32_t n = meta[k].n_out, st = gz_reach_status(meta[k], text, window_in != nullptr);
         if (st && !bad) bad = st, bad_at = k;
         if (meta[k].final_block) fin = k + 1u;
         if (tid == 0) meta[k].text_off = text;
@@ -694,10 +709,7 @@ __global__ __launch_bounds__(1024) void k_gz_win_chain(const uint16_t *__restric
     for (uint32_t i0 = 0; i0 < n_chunks; i0 += 1024u) {
         const uint32_t i = i0 + tid;
         const u64 v = i < n_chunks ? meta[i].n_out : 0;
-        if (i < n_chunks) {
-            if (meta[i].status) atomicMin(&s_bad_at, i);
-            if (meta[i].final_block) atomicMax(&s_fin, i + 1u);
-        }
+        if (i < n_chunks && meta[i].final_block) atomicMax(&s_fin, i + 1u);
         u64 inc = v;
 #pragma unroll
         for (int o = 1; o < kWave; o <<= 1) {
@@ -708,7 +720,11 @@ __global__ __launch_bounds__(1024) void k_gz_win_chain(const uint16_t *__restric
         __syncthreads();
         u64 before = s_carry;
         for (int w = 0; w < wave_id(); ++w) before += s_wave[w];
-        if (i < n_chunks) meta[i].text_off = before + inc - v;
+        if (i < n_chunks) {
+            meta[i].text_off = before + inc - v;
+            const uint32_t st = gz_reach_status(meta[i], before + inc - v, window_in != nullptr);
+            if (st) meta[i].status = st, atomicMin(&s_bad_at, i);
+        }
         __syncthreads();
         if (tid == 1023) s_carry = before + inc;
         __syncthreads();

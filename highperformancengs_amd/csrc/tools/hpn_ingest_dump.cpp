@@ -71,9 +71,10 @@ int main(int argc, char **argv)
             fwrite(buf.data(), 1, (size_t)n, stdout);
         }
         if (test_env("HPN_READER_STATS"))  // which reader produced the stream, and how
-            fprintf(stderr, "reader=%s accepted=%lu gaps=%lu fallback=%d crc_failed=%d find_s=%.3f decode_s=%.3f translate_s=%.3f\n",
+            fprintf(stderr, "reader=%s accepted=%lu gaps=%lu fallback=%d crc_failed=%d handed_back=%lu find_s=%.3f decode_s=%.3f translate_s=%.3f\n",
                     f.pz ? "pgz" : f.mz ? "mgz" : f.bz ? "bgzf" : "zlib", f.pz ? (unsigned long)f.pz->chunks_accepted() : 0ul,
                     f.pz ? (unsigned long)f.pz->gaps_decoded() : 0ul, f.pz ? (int)f.pz->fell_back() : 0, f.pz ? (int)f.pz->crc_failed() : 0,
+                    f.mz ? f.mz->handed_back() : 0ul,   // (members the quick decoder gave back to zlib: tests/test_deflate_craft_host.py)
                     f.pz ? f.pz->seconds_find() : 0.0, f.pz ? f.pz->seconds_decode() : 0.0, f.pz ? f.pz->seconds_translate() : 0.0);
         if (f.damaged()) fprintf(stderr, "damaged\n");   // (what makes the tools read the file again, the reference's way)
         f.close();

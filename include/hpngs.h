@@ -457,7 +457,8 @@ int hpn_bgzf_inflate_dev(hpn_ctx *ctx, const uint8_t *d_comp, const hpn_bgzf_blo
  * status codes: 1-11 malformed block header or code tables, 12/14 out of symbol scratch (sym_cap), 13/15 invalid
  * code in the data, 17 ran past in_len, 20 the stretch did not end on end_bit at a block boundary, 22 a final block
  * inside a stretch that was given an end and nothing that starts another member behind it (the next stretch's start is
- * unproven), 23 more members ended inside the call than it has room for (65536), 24 a header too long to back out of.
+ * unproven), 23 more members ended inside the call than it has room for (65536), 24 a header too long to back out of,
+ * 25 a match that reaches in front of the stream's first byte (d_window_in NULL: the call starts the stream).
  *
  * Several members (cat a.gz b.gz): a stretch that meets a final block looks behind the 8-byte trailer for the next
  * member's header (RFC 1952) and goes on with its first block.  hpn_gz_members() lists the members that ended inside the
