@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import orc
+from tally_ref import nuc_ref as _nuc_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -35,19 +36,6 @@ def _check(ctx, qual, off, base=None, full=True):
         if base is not None:
             assert np.array_equal(got.nuc_hist, _nuc_ref(base, off))
     return want
-
-
-def _nuc_ref(base, off):
-    """Nucleotide[5][512] per Rgzfastq_uniq.c:50-57,97-108 (numpy restatement for the test)."""
-    lut = np.zeros(256, np.int64)
-    for ch, v in ((b"tTuU", 0), (b"cC", 1), (b"aA", 2), (b"gG", 3), (b".N", 4)):
-        for c in ch:
-            lut[c] = v
-    out = np.zeros((5, 512), np.uint64)
-    lens = np.diff(off.astype(np.int64))
-    pos = np.arange(int(off[-1] - off[0])) - np.repeat(off[:-1].astype(np.int64) - int(off[0]), lens)
-    np.add.at(out, (lut[base[int(off[0]):int(off[-1])]], pos), 1)
-    return out
 
 
 def test_appendix_a1_batch(ctx):
