@@ -62,6 +62,14 @@ class UniqResult(C.Structure):
 UNIQ_TABLE_ORDER, UNIQ_KEY_ORDER = 0, 1
 
 
+class UniqqResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_unique", C.c_uint64), ("hash_size", C.c_uint64), ("hash_clashes", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("max_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+UNIQQ_KEY_ORDER, UNIQQ_COUNT_ORDER = 0, 1
+
+
 class SortInfo(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -153,6 +161,10 @@ SYMBOLS = [
     ("hpn_fastq_uniq_finish", _int, [_vp, C.POINTER(UniqResult)]),
     ("hpn_fastq_uniq_write", _int, [_vp, _int, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_sort_pairs_u64", _int, [_vp, _vp, _vp, _u64]),
+    ("hpn_fastq_uniqq_begin", _int, [_vp, _u64, _u32]),
+    ("hpn_fastq_uniqq_add", _int, [_vp, _vp, _u64, _int, C.POINTER(UniqInfo)]),
+    ("hpn_fastq_uniqq_finish", _int, [_vp, C.POINTER(UniqqResult)]),
+    ("hpn_fastq_uniqq_write", _int, [_vp, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_fastq_sort_begin", _int, [_vp, _int, _u64]),
     ("hpn_fastq_sort_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
     ("hpn_fastq_sort_finish", _int, [_vp, C.POINTER(SortResult)]),
@@ -218,7 +230,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 4:
+    if L.hpn_abi_version() != 5:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -277,6 +277,34 @@ class Context:
             parts.append(buf[:got.value].tobytes())
             at += got.value
 
+    # ---- duplicate removal that keeps every quality line (gzfastq_uniqQ) ----------------------
+    def uniqq_begin(self, max_bytes=0, hash_bits=0):
+        self._ck(self.L.hpn_fastq_uniqq_begin(self.h, int(max_bytes), int(hash_bits)), "hpn_fastq_uniqq_begin")
+
+    def uniqq_add(self, chunk, last=False):
+        """One chunk of FASTQ text into the session's device store; returns the hpn_uniq_info."""
+        chunk, n = self._text(chunk)
+        info = _lib.UniqInfo()
+        self._ck(self.L.hpn_fastq_uniqq_add(self.h, _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_fastq_uniqq_add")
+        return info
+
+    def uniqq_finish(self):
+        res = _lib.UniqqResult()
+        self._ck(self.L.hpn_fastq_uniqq_finish(self.h, C.byref(res)), "hpn_fastq_uniqq_finish")
+        return res
+
+    def uniqq_output(self, which=_lib.UNIQQ_KEY_ORDER, slice_bytes=1 << 24):
+        """The whole text of one output, fetched in slices (hpn_fastq_uniqq_write)."""
+        parts, at = [], 0
+        buf = np.zeros(max(int(slice_bytes), 1), np.uint8)
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_fastq_uniqq_write(self.h, int(which), at, _ptr(buf), buf.size, C.byref(got)), "hpn_fastq_uniqq_write")
+            if not got.value:
+                return b"".join(parts)
+            parts.append(buf[:got.value].tobytes())
+            at += got.value
+
     # ---- the whole file ordered by name or sequence (gzfastq_sort) ---------------------------
     def sort_begin(self, by_name=False, max_bytes=0):
         self._ck(self.L.hpn_fastq_sort_begin(self.h, int(bool(by_name)), int(max_bytes)), "hpn_fastq_sort_begin")

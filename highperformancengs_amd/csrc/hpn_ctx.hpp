@@ -12,6 +12,7 @@
 struct hpn_ctx;
 struct hpn_uniq_state;   // hpn_uniq.hip
 struct hpn_sort_state;   // hpn_sort.hip
+struct hpn_uniqq_state;  // hpn_uniqq.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -93,6 +94,7 @@ struct hpn_ctx {
     bool r_fields = false;  // the SoA view of the current index has been gathered
     hpn_uniq_state *uq = nullptr;   // hpn_fastq_uniq_*: the store, the descriptors, the sorts' arrays
     hpn_sort_state *sq = nullptr;   // hpn_fastq_sort_*: the same for the whole-file sort
+    hpn_uniqq_state *qq = nullptr;  // hpn_fastq_uniqq_*: a uniq session of its own and the members' placement
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -121,6 +123,7 @@ inline int fail(hpn_ctx *c, int status, const char *fmt, ...)
 
 void uniq_release(hpn_ctx *c);   // hpn_uniq.hip
 void sort_release(hpn_ctx *c);   // hpn_sort.hip
+void uniqq_release(hpn_ctx *c);  // hpn_uniqq.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

@@ -26,17 +26,9 @@
 // kept record once.
 #include "radix_sort.hpp"
 #include "text_common.hpp"
+#include "uniq_desc.hpp"
 
 namespace hpn {
-
-struct UniqDesc {
-    u64 off;         // where the record's name line starts in the store
-    u64 h0;          // sum of c[i] * B^(L-1-i) modulo 2^64 over the sequence
-    uint32_t d0;     // the same with 33 modulo 2^32
-    uint32_t sumq;   // sum of the first min(slen, qlen) quality bytes
-    uint16_t nlen, slen, qlen, qrel;   // name, sequence, quality as the reference keeps them; quality's offset from `off`
-};
-static_assert(sizeof(UniqDesc) == 32, "UniqDesc is one 32-byte granule");
 
 struct UniqView {
     const uint8_t *text[2];
@@ -67,15 +59,11 @@ __device__ __forceinline__ u64 powB(uint32_t e)   // e < 4096
     return r;
 }
 
-__device__ __forceinline__ uint32_t uniq_digits(uint32_t v)
-{
-    uint32_t d = 1;
-    for (uint32_t p = 10; d < 10u && v >= p; p *= 10) ++d;
-    return d;
-}
-
 // Launched with an upper bound of workgroups (the line count lives on the device).  st: the state block k_text_lines
-// left; desc: where this chunk's first descriptor goes; origin: the store offset of slot[begin].
+// left; desc: where this chunk's first descriptor goes; origin: the store offset of slot[begin].  kShortQual: a quality line two
+// or more bytes shorter than its sequence is irregular (gzfastq_uniq.c sums bytes outside its buffer; gzfastq_uniqQ.c prints
+// nothing of its sum, so hpn_fastq_uniqq_add takes such lines: sumq is then the sum over the bytes there are).
+template <bool kShortQual>
 __global__ __launch_bounds__(kTxtThreads) void k_uniq_keys(const uint8_t *__restrict__ slot, const uint32_t *__restrict__ nl,
                                                            uint32_t begin, uint32_t end, int last, u64 origin,
                                                            UniqDesc *__restrict__ desc, uint32_t *__restrict__ st)
@@ -113,7 +101,7 @@ __global__ __launch_bounds__(kTxtThreads) void k_uniq_keys(const uint8_t *__rest
         qs = e[2] + 1u, lq = e[3] - e[2] - 1u - (open_end ? 1u : 0u);   // a last line without '\n' loses a real byte
         uint32_t f = 0;
         if (e[0] - prev > 1023u || e[1] - e[0] > 1023u || e[2] - e[1] > 1023u || e[3] - e[2] > 1023u) f |= HPN_TEXT_LONG_LINE;  // gzgets would split it
-        else if (lq + 1u < ls) f |= HPN_TEXT_SHORT_QUAL;   // the reference would sum bytes outside its buffer
+        else if (kShortQual && lq + 1u < ls) f |= HPN_TEXT_SHORT_QUAL;   // the reference would sum bytes outside its buffer
         if (f) {
             atomicOr(&st[kTsFlags], f);
             ls = lq = 0;   // (the chunk is refused anyway: keep the loads inside it)
@@ -395,7 +383,15 @@ static inline unsigned blocks256(uint32_t n) { return n ? (n + 255u) / 256u : 1u
 hipError_t launch_uniq_keys(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_uniq_keys, dim3(max_records / kTxtThreads + 1u), dim3(kTxtThreads), 0, st, d_slot, d_nl, begin, end, last,
+    hipLaunchKernelGGL(k_uniq_keys<true>, dim3(max_records / kTxtThreads + 1u), dim3(kTxtThreads), 0, st, d_slot, d_nl, begin, end, last,
+                       (u64)origin, (UniqDesc *)d_desc, d_state);
+    return hipGetLastError();
+}
+
+hipError_t launch_uniqq_keys(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
+                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_uniq_keys<false>, dim3(max_records / kTxtThreads + 1u), dim3(kTxtThreads), 0, st, d_slot, d_nl, begin, end, last,
                        (u64)origin, (UniqDesc *)d_desc, d_state);
     return hipGetLastError();
 }
@@ -500,6 +496,11 @@ hipError_t uniq_scan32(const uint32_t *d_in, uint32_t *d_out, uint64_t n, u64 *d
 hipError_t uniq_scan64(const uint32_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st)
 {
     return launch_excl_scan<uint32_t, uint64_t>(d_in, d_out, n, d_status, d_ticket, d_err, st);
+}
+// 64-bit items (hpn_fastq_uniqq_*: a group's bytes -- one group of quality lines can pass 4 GiB)
+hipError_t uniq_scan64w(const uint64_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st)
+{
+    return launch_excl_scan<uint64_t, uint64_t>(d_in, d_out, n, d_status, d_ticket, d_err, st);
 }
 uint64_t uniq_scan_tiles(uint64_t n) { return scan_tiles(n); }
 uint64_t uniq_sort_hist_words(uint32_t n) { return sort_hist_words(n); }

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 4
+#define HPN_ABI_VERSION 5
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -348,6 +348,44 @@ int hpn_fastq_uniq_write(hpn_ctx *ctx, int which_output, int mate, uint64_t offs
 /* The stable radix sort behind it on its own: n < 2^31 pairs, ascending by key, equal keys in their given order.
  * keys and vals: host or device pointers, sorted in place. */
 int hpn_sort_pairs_u64(hpn_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n);
+
+/* ---- gzfastq_uniqQ.c: one group per distinct sequence, every copy's quality line kept ---------------------
+ * The reads of one stream are collapsed by their sequence like hpn_fastq_uniq_* collapses them, framed by the same
+ * readNextNode (gzfastq_uniqQ.c:181-203), but every record stays in its key's list, new records at the head
+ * (list_add_data, list.c; gzfastq_uniqQ.c:220, :229).  An output group is "name\tcount\nsequence\n+\n" with the name of the
+ * LAST record read that carries the sequence (:86), and then one "quality\n" per member, from the last record read to the
+ * first (:67-76).  The quality sum (:217) is never printed: a quality line shorter than its sequence is regular here.
+ *
+ *   hpn_fastq_uniqq_begin   opens a session (closing the context's earlier one; a hpn_fastq_uniq session is another one and
+ *                           stays).  max_bytes and hash_bits: as for hpn_fastq_uniq_begin.
+ *   hpn_fastq_uniqq_add     one chunk (the chunk contract of hpn_fastq_uniq_add: cut anywhere, host or device pointer, `last`
+ *                           closes the stream).  Irregular text -- HPN_TEXT_NUL, _LONG_LINE, _PARTIAL, _DENSE -- is reported in
+ *                           info->irregular and closes the session; HPN_TEXT_SHORT_QUAL is never raised.  HPN_E_CAPACITY and
+ *                           HPN_E_DOMAIN (2^31 or more records) as there.
+ *   hpn_fastq_uniqq_finish  after the last chunk: groups, orders, fills *result.  hash_size: the reference only ever calls
+ *                           dictAdd (:221), so its table has the smallest power of two >= max(n_unique, 4) slots (0 without a
+ *                           record).
+ *   hpn_fastq_uniqq_write   copies up to `cap` bytes of an output (result->out_bytes in either order), from byte `offset` on, to
+ *                           `out` (host or device).  HPN_UNIQQ_KEY_ORDER: keys ascending by memcmp, then length (-S,
+ *                           compare_hashed_key :246-248).  HPN_UNIQQ_COUNT_ORDER: count descending, equal counts in the order in
+ *                           which the reference walks its table (-C, compare_hashed_data_count :242-244 under glibc's stable
+ *                           qsort over dump_dict's array :250-261).  Reading one output front to back before the other costs
+ *                           one formatting pass per output. */
+typedef struct hpn_uniqq_result {
+    uint64_t n_records;    /* records that were keyed */
+    uint64_t n_unique;     /* distinct keys */
+    uint64_t hash_size;    /* the size the reference's table would have ("hash size: ") */
+    uint64_t hash_clashes; /* records whose grouping hash equalled their neighbour's over different bytes */
+    uint64_t out_bytes;    /* bytes of the output (the same in both orders) */
+    uint32_t max_count;    /* the largest group */
+    uint32_t reserved;
+} hpn_uniqq_result;
+#define HPN_UNIQQ_KEY_ORDER 0
+#define HPN_UNIQQ_COUNT_ORDER 1
+int hpn_fastq_uniqq_begin(hpn_ctx *ctx, uint64_t max_bytes, uint32_t hash_bits);
+int hpn_fastq_uniqq_add(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info);
+int hpn_fastq_uniqq_finish(hpn_ctx *ctx, hpn_uniqq_result *result);
+int hpn_fastq_uniqq_write(hpn_ctx *ctx, int which_output, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
 
 /* ---- gzfastq_sort.c: the whole file ordered by name or by sequence ---------------------------------------
  * The records of one stream, framed as readNextNode frames them (see above), in ascending order of their KEY LINE -- the
