@@ -70,6 +70,15 @@ class UniqqResult(C.Structure):
 UNIQQ_KEY_ORDER, UNIQQ_COUNT_ORDER = 0, 1
 
 
+class UsortResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_unique", C.c_uint64), ("table_reads", C.c_uint64), ("hash_size", C.c_uint64),
+                ("unmatched", C.c_int64), ("out_bytes", C.c_uint64 * 2), ("hash_clashes", C.c_uint64), ("max_count", C.c_uint32),
+                ("seq_len", C.c_uint32), ("no_answer", C.c_uint32), ("reserved", C.c_uint32), ("unmatched_name", C.c_char * 1024)]
+
+
+USORT_FEW_READS, USORT_LONG_KEY, USORT_SHORT_KEY = 1, 2, 3
+
+
 class SortInfo(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -165,6 +174,10 @@ SYMBOLS = [
     ("hpn_fastq_uniqq_add", _int, [_vp, _vp, _u64, _int, C.POINTER(UniqInfo)]),
     ("hpn_fastq_uniqq_finish", _int, [_vp, C.POINTER(UniqqResult)]),
     ("hpn_fastq_uniqq_write", _int, [_vp, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_fastq_usort_begin", _int, [_vp, _int, _u64, _u32]),
+    ("hpn_fastq_usort_add", _int, [_vp, _int, _vp, _u64, _int, C.POINTER(UniqInfo)]),
+    ("hpn_fastq_usort_finish", _int, [_vp, C.POINTER(UsortResult)]),
+    ("hpn_fastq_usort_write", _int, [_vp, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_fastq_sort_begin", _int, [_vp, _int, _u64]),
     ("hpn_fastq_sort_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
     ("hpn_fastq_sort_finish", _int, [_vp, C.POINTER(SortResult)]),

@@ -277,6 +277,38 @@ class Context:
             parts.append(buf[:got.value].tobytes())
             at += got.value
 
+    # ---- duplicate removal, most frequent first (gzfastq_uniq_sort) ---------------------------
+    def usort_begin(self, paired=False, max_bytes=0, hash_bits=0):
+        self._ck(self.L.hpn_fastq_usort_begin(self.h, int(bool(paired)), int(max_bytes), int(hash_bits)), "hpn_fastq_usort_begin")
+
+    def usort_add(self, chunk, mate=0, last=False):
+        """One chunk of FASTQ text of one mate into the session's device store; returns the hpn_uniq_info."""
+        chunk, n = self._text(chunk)
+        info = _lib.UniqInfo()
+        self._ck(self.L.hpn_fastq_usort_add(self.h, int(mate), _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_fastq_usort_add")
+        return info
+
+    def usort_finish(self):
+        """The hpn_usort_result.  Where the reference has no answer (HPN_E_DOMAIN) the result comes back with no_answer set
+        instead of an exception: there is no output then."""
+        res = _lib.UsortResult()
+        rc = self.L.hpn_fastq_usort_finish(self.h, C.byref(res))
+        if not (rc == _lib.E_DOMAIN and res.no_answer):
+            self._ck(rc, "hpn_fastq_usort_finish")
+        return res
+
+    def usort_output(self, mate=0, slice_bytes=1 << 24):
+        """The whole text of one mate's output, fetched in slices (hpn_fastq_usort_write)."""
+        parts, at = [], 0
+        buf = np.zeros(max(int(slice_bytes), 1), np.uint8)
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_fastq_usort_write(self.h, int(mate), at, _ptr(buf), buf.size, C.byref(got)), "hpn_fastq_usort_write")
+            if not got.value:
+                return b"".join(parts)
+            parts.append(buf[:got.value].tobytes())
+            at += got.value
+
     # ---- duplicate removal that keeps every quality line (gzfastq_uniqQ) ----------------------
     def uniqq_begin(self, max_bytes=0, hash_bits=0):
         self._ck(self.L.hpn_fastq_uniqq_begin(self.h, int(max_bytes), int(hash_bits)), "hpn_fastq_uniqq_begin")

@@ -20,6 +20,7 @@
 #include <string>
 
 #include "../host/fastq_reader.hpp"
+#include "../host/mem_lines.hpp"
 #include "../host/report.hpp"
 #include "../host/text_feed.hpp"
 
@@ -81,39 +82,8 @@ static bool device_feed(hpn_ctx *ctx, const char *path)
 // the whole inflated stream in memory (standard input, which cannot be read twice; a file whose text is not regular)
 static void slurp(const char *path, std::string &mem)
 {
-    InStream in = open_input_stream(path);
-    std::vector<char> buf((size_t)1 << 20);
-    for (;;) {
-        const int k = in.read(buf.data(), (unsigned)buf.size());
-        if (k <= 0) break;
-        mem.append(buf.data(), (size_t)k);
-    }
-    const bool damaged = in.damaged();
-    in.close();
-    if (damaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+    if (!slurp_stream(path, mem)) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
 }
-
-// gzgets(file, buf, 1024) and gzeof over the stream in memory
-struct MemLines {
-    const std::string &d;
-    size_t pos = 0;
-    bool past = false;
-    explicit MemLines(const std::string &s) : d(s) {}
-    bool gets(const char **p, size_t *n)
-    {
-        if (pos >= d.size()) {
-            past = true;
-            return false;
-        }
-        const size_t room = d.size() - pos < (size_t)kLineBuf - 1 ? d.size() - pos : (size_t)kLineBuf - 1;
-        const void *nl = memchr(d.data() + pos, '\n', room);
-        size_t k = nl ? (size_t)((const char *)nl - (d.data() + pos)) + 1 : room;
-        if (!nl && pos + k == d.size() && k < (size_t)kLineBuf - 1) past = true;
-        *p = d.data() + pos, *n = k;
-        pos += k;
-        return true;
-    }
-};
 
 // readNextNode (gzfastq_uniqQ.c:181-203) over the stream in memory: the gzeof test sits behind the FIRST gzgets only.  The
 // records go out as canonical text -- every line without its last byte and closed -- which the device frames like any

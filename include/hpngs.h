@@ -387,6 +387,53 @@ int hpn_fastq_uniqq_add(hpn_ctx *ctx, const void *text, uint64_t nbytes, int las
 int hpn_fastq_uniqq_finish(hpn_ctx *ctx, hpn_uniqq_result *result);
 int hpn_fastq_uniqq_write(hpn_ctx *ctx, int which_output, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
 
+/* ---- gzfastq_uniq_sort.c: one record per distinct sequence, most frequent first ---------------------------
+ * The reads of one stream (or the pairs of two) are collapsed by their sequence (pairs: by both sequences joined) like
+ * hpn_fastq_uniq_* collapses them, framed by the same readNextNode (gzfastq_uniq_sort.c:67-88); a quality line shorter than its
+ * sequence is regular (nothing reads it against the sequence).  Per key: the number of records, and as representative the
+ * FIRST record that carries it (:147-159).  The keys come by count descending; equal counts in the order in which the
+ * reference walks its table (hashtbl.c): a table of S = (size_t)(1.34 * e) slots that never resizes, e = the groups of four
+ * lines that count_read (:174-185) sees in mate 0 -- one open line behind the last record counts --, slot =
+ * djb2 over 64 bits modulo S, every chain newest key first.  An output record is "name\tcount\nSEQ\n+\nquality\n"; SEQ of
+ * mate 0 is the first seq_len bytes of the joined key (a shorter key whole), SEQ of mate 1 the bytes behind them; seq_len is the
+ * length of the first mate-0 sequence that is not empty (:129).
+ *
+ *   hpn_fastq_usort_begin   opens a session (closing the context's earlier one; sessions of hpn_fastq_uniq_* and _uniqq_* are
+ *                           others and stay).  paired, max_bytes and hash_bits: as for hpn_fastq_uniq_begin.
+ *   hpn_fastq_usort_add     the chunk contract of hpn_fastq_uniq_add.  Irregular text -- HPN_TEXT_NUL, _LONG_LINE, _PARTIAL,
+ *                           _DENSE -- is reported in info->irregular and closes the session; HPN_TEXT_SHORT_QUAL is never raised.
+ *                           HPN_E_CAPACITY and HPN_E_DOMAIN (2^31 or more records) as there.
+ *   hpn_fastq_usort_finish  after every mate's last chunk: groups, orders, fills *result.  Pairs stop at the first ordinal
+ *                           without a matching mate as in hpn_fastq_uniq_finish.  Where the reference has no answer the call
+ *                           returns HPN_E_DOMAIN, result->no_answer tells why and the session is closed:
+ *                           HPN_USORT_FEW_READS  e < 10 and at least one record: the reference divides by e / 10 (:161);
+ *                           HPN_USORT_LONG_KEY   a pair's joined sequences have more than 1023 bytes (pair_seq, :125);
+ *                           HPN_USORT_SHORT_KEY  a pair's joined sequences have fewer than seq_len bytes (key + strLen, :227).
+ *   hpn_fastq_usort_write   copies up to `cap` bytes of the output of mate `mate` (result->out_bytes[mate]), from byte `offset`
+ *                           on, to `out` (host or device).  Reading one output front to back before the other costs one
+ *                           formatting pass per output. */
+typedef struct hpn_usort_result {
+    uint64_t n_records;    /* records (pairs) that were keyed ("total reads = ") */
+    uint64_t n_unique;     /* distinct keys */
+    uint64_t table_reads;  /* e ("total_reads_num: ") */
+    uint64_t hash_size;    /* S ("hash size: ") */
+    int64_t unmatched;     /* pairs: the first ordinal without a matching mate, else -1 */
+    uint64_t out_bytes[2]; /* bytes of the outputs of mate 0 and mate 1 */
+    uint64_t hash_clashes; /* records whose grouping hash equalled their neighbour's over different bytes */
+    uint32_t max_count;    /* the largest group */
+    uint32_t seq_len;      /* strLen */
+    uint32_t no_answer;    /* 0, or HPN_USORT_* with HPN_E_DOMAIN */
+    uint32_t reserved;
+    char unmatched_name[1024];
+} hpn_usort_result;
+#define HPN_USORT_FEW_READS 1u
+#define HPN_USORT_LONG_KEY 2u
+#define HPN_USORT_SHORT_KEY 3u
+int hpn_fastq_usort_begin(hpn_ctx *ctx, int paired, uint64_t max_bytes, uint32_t hash_bits);
+int hpn_fastq_usort_add(hpn_ctx *ctx, int mate, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info);
+int hpn_fastq_usort_finish(hpn_ctx *ctx, hpn_usort_result *result);
+int hpn_fastq_usort_write(hpn_ctx *ctx, int mate, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
+
 /* ---- gzfastq_sort.c: the whole file ordered by name or by sequence ---------------------------------------
  * The records of one stream, framed as readNextNode frames them (see above), in ascending order of their KEY LINE -- the
  * whole name line with its '@' and comment (by_name) or the sequence line: first by its length, then by its bytes compared as
