@@ -87,6 +87,10 @@ class SortResult(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64), ("refined", C.c_uint64), ("rounds", C.c_uint32), ("lone_line", C.c_uint32)]
 
 
+class TwobitResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64), ("bad_record", C.c_int64), ("seq_len", C.c_uint32), ("packed_len", C.c_uint32)]
+
+
 class TextPiece(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -182,6 +186,11 @@ SYMBOLS = [
     ("hpn_fastq_sort_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
     ("hpn_fastq_sort_finish", _int, [_vp, C.POINTER(SortResult)]),
     ("hpn_fastq_sort_write", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_twobit_pack_begin", _int, [_vp, _u64]),
+    ("hpn_twobit_pack_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
+    ("hpn_twobit_pack_finish", _int, [_vp, C.POINTER(TwobitResult)]),
+    ("hpn_twobit_pack_write", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_twobit_unpack", _int, [_vp, _u32, _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_fastq_text_piece_lines", _int, [_vp, _vp, _u64, _u32, _u64, _int, C.POINTER(TextPiece)]),
     ("hpn_fastq_text_piece_count", _int, [_vp, _u64, _u32, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_piece_trim", _int, [_vp, _u64, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
@@ -243,7 +252,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 5:
+    if L.hpn_abi_version() != 6:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -365,6 +365,49 @@ class Context:
             parts.append(buf[:got.value].tobytes())
             at += got.value
 
+    # ---- the sequences packed to 2 bits per base, and back (fastq2twobit, twoBit2seq) ---------
+    def twobit_pack_begin(self, max_bytes=0):
+        self._ck(self.L.hpn_twobit_pack_begin(self.h, int(max_bytes)), "hpn_twobit_pack_begin")
+
+    def twobit_pack_add(self, chunk, last=False):
+        """One chunk of FASTQ text into the session's device store; returns the hpn_sort_info."""
+        chunk, n = self._text(chunk)
+        info = _lib.SortInfo()
+        self._ck(self.L.hpn_twobit_pack_add(self.h, _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_twobit_pack_add")
+        return info
+
+    def twobit_pack_finish(self):
+        res = _lib.TwobitResult()
+        self._ck(self.L.hpn_twobit_pack_finish(self.h, C.byref(res)), "hpn_twobit_pack_finish")
+        return res
+
+    def twobit_pack_output(self, slice_bytes=1 << 24):
+        """The whole packed output, fetched in slices (hpn_twobit_pack_write)."""
+        parts, at = [], 0
+        buf = np.zeros(max(int(slice_bytes), 1), np.uint8)
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_twobit_pack_write(self.h, at, _ptr(buf), buf.size, C.byref(got)), "hpn_twobit_pack_write")
+            if not got.value:
+                return b"".join(parts)
+            parts.append(buf[:got.value].tobytes())
+            at += got.value
+
+    def twobit_unpack(self, seq_len, packed_len, packed, n_records, out=None):
+        """n_records records of packed_len bytes -> text (hpn_twobit_unpack).  packed: bytes / numpy (host) or a device array; out: None
+        (a host buffer is made and its bytes returned) or a device array of enough bytes (returns the byte count)."""
+        if isinstance(packed, (bytes, bytearray)):
+            packed = np.frombuffer(bytes(packed), np.uint8)
+        need = int(n_records) * (int(seq_len) + 1)
+        got = C.c_uint64(0)
+        if out is None:
+            buf = np.zeros(max(need, 1), np.uint8)
+            self._ck(self.L.hpn_twobit_unpack(self.h, int(seq_len), int(packed_len), _ptr(packed), int(n_records), _ptr(buf), need, C.byref(got)), "hpn_twobit_unpack")
+            return buf[:got.value].tobytes()
+        self._ck(self.L.hpn_twobit_unpack(self.h, int(seq_len), int(packed_len), _ptr(packed), int(n_records), _ptr(out), int(out.numel() * out.element_size()),
+                                          C.byref(got)), "hpn_twobit_unpack")
+        return got.value
+
     def sort_pairs(self, keys, vals):
         """Stable ascending sort of uint64 keys with their uint32 payload on the device (hpn_sort_pairs_u64); returns copies."""
         keys, vals = np.array(keys, np.uint64), np.array(vals, np.uint32)

@@ -14,6 +14,7 @@ struct hpn_uniq_state;   // hpn_uniq.hip
 struct hpn_sort_state;   // hpn_sort.hip
 struct hpn_uniqq_state;  // hpn_uniqq.hip
 struct hpn_usort_state;  // hpn_usort.hip
+struct hpn_twobit_state; // hpn_twobit.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -97,6 +98,7 @@ struct hpn_ctx {
     hpn_sort_state *sq = nullptr;   // hpn_fastq_sort_*: the same for the whole-file sort
     hpn_uniqq_state *qq = nullptr;  // hpn_fastq_uniqq_*: a uniq session of its own and the members' placement
     hpn_usort_state *us = nullptr;  // hpn_fastq_usort_*: a uniq session of its own, the 64-bit djb2 and the count order
+    hpn_twobit_state *tb = nullptr; // hpn_twobit_pack_*: the store, the sizes and offsets, the packed output
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -127,6 +129,7 @@ void uniq_release(hpn_ctx *c);   // hpn_uniq.hip
 void sort_release(hpn_ctx *c);   // hpn_sort.hip
 void uniqq_release(hpn_ctx *c);  // hpn_uniqq.hip
 void usort_release(hpn_ctx *c);  // hpn_usort.hip
+void twobit_release(hpn_ctx *c); // hpn_twobit.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

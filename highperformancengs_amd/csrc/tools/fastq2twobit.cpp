@@ -1,0 +1,189 @@
+// fastq2twobit -- drop-in for the reference tool of the same name (fastq2twobit.c with the packing of twoBit.h): the sequences of
+// a plain or gzip FASTQ file (or of standard input) packed to 2 bits per base; framing and packing run on MI355X through libhpngs.
+//
+//   fastq2twobit [-i FILE] [-o PREFIX] [-s|-n] [-h]
+//
+//   -i        default "-": standard input.   -o  PREFIX_sort_by_seq.fq / PREFIX_sort_by_name.fq; a prefix that begins with '-'
+//             (the default) means standard output.   -s / -n  choose that NAME only (the last one given wins): nothing is sorted.
+//   output    the reference pushes every record on the front of a list and dumps the list: the records come in REVERSE input
+//             order.  Two header bytes -- the length and the packed length of the input's LAST record, modulo 256 -- and then
+//             (len + 3) >> 2 bytes per record: four bases per byte, the first in the top bits, C 1, A 2, G 3 in either case,
+//             every other byte 0, the last byte's tail 0.  No record: an empty file.
+//   stderr    the reference's lines: "name: a\tseq: b", "done read file at T s", "list count: N", four more "done ... at T s".
+//
+// Where the reference has no answer -- a file that ends inside a record, a line of 1023+ characters, a damaged gzip stream, a
+// sequence byte of 0x80 or more (it indexes its table with a signed char) -- this tool says so and leaves with status 2.  The
+// reads are held in the memory of ONE device: an input beyond that is refused with the number of bytes that were needed.
+#include <getopt.h>
+
+#include <string>
+
+#include "../host/mem_lines.hpp"
+#include "../host/report.hpp"
+#include "../host/text_feed.hpp"
+
+using namespace hpn;
+
+static void usage(const char *prog)
+{
+    fprintf(stderr,
+            "\nUsage: %s [-i Infile] [-o OUTFILE] [-s|-n] [-h]\n"
+            "  Packs the sequences of a plain or gzip FASTQ file to 2 bits per base, the reads in reverse input order behind\n"
+            "  a 2-byte header (MI355X build of HighPerformanceNGS fastq2twobit; twoBit2seq is the inverse).\n"
+            "Example1:\n  zcat reads.fastq.gz | %s -o out\n\n"
+            "   [-i Infile] = Infile, default standard input.                    [option]\n"
+            "   [-o OUTPUT] = prefix of OUTPUT_sort_by_seq.fq / _sort_by_name.fq,\n"
+            "                 default (or a leading '-') standard output.        [option]\n"
+            "   [-s ] name the output _sort_by_seq.fq (default).                 [option]\n"
+            "   [-n ] name the output _sort_by_name.fq.                          [option]\n"
+            "   [-h] This helpful help screen.                                   [option]\n\n",
+            prog, prog);
+    exit(1);
+}
+
+[[noreturn]] static void refuse(const char *path, const char *why)
+{
+    fprintf(stderr, "fastq2twobit: %s: %s (the reference has no answer there)\n", path, why);
+    leave(2);
+}
+
+static bool add_chunk(hpn_ctx *ctx, const void *text, uint64_t n, bool last, uint64_t *records)
+{
+    hpn_sort_info si;
+    const int rc = hpn_twobit_pack_add(ctx, text, n, last, &si);
+    if (rc == HPN_E_CAPACITY) {
+        fprintf(stderr, "fastq2twobit: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
+        leave(2);
+    }
+    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_twobit_pack_add");
+    *records += si.n_records;
+    return si.irregular == 0;
+}
+
+// The file's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
+struct FileSink {
+    hpn_ctx *ctx;
+    uint64_t *records;
+    void route_begins() {}
+    bool start_over() { return false; }   // the session is void: the caller begins a new one
+    bool chunk(const void *text, uint64_t n, bool last) { return add_chunk(ctx, text, n, last, records); }
+};
+
+// A file into the session on the device.  false: the text is not regular (or a route gave up half way) -- the session is void
+// and the caller frames the file on the host.
+static bool device_feed(hpn_ctx *ctx, const char *path, uint64_t *records)
+{
+    FileSink sink{ctx, records};
+    const FeedEnd end = feed_fastq_file(ctx, path, "fastq2twobit", sink);
+    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+    return end == FeedEnd::kDone;
+}
+
+// readNextNode (fastq2twobit.c, the same as gzfastq_sort.c:143-165) over the stream in memory: the gzeof test sits behind the
+// FIRST gzgets only.  The records go out as canonical text -- the fields as strlen sees them, every line closed -- which the
+// device frames like any regular chunk.  Refuses what the reference crashes on.
+static void host_feed(hpn_ctx *ctx, const char *path, const std::string &mem, uint64_t *records)
+{
+    MemLines in(mem);
+    std::string text;
+    const size_t kFlush = (size_t)8 << 20;
+    auto field = [&](bool have, const char *p, size_t n) {   // what strlen sees, without its last byte
+        if (!have) refuse(path, "the file ends inside a record");
+        if (n == (size_t)kLineBuf - 1 && p[n - 1] != '\n') refuse(path, "line of 1023 or more characters");
+        const size_t l = strnlen(p, n);
+        if (!l) refuse(path, "line that starts with a NUL byte");
+        text.append(p, l - 1).push_back('\n');
+    };
+    for (;;) {
+        const char *p;
+        size_t n;
+        bool have = in.gets(&p, &n);
+        if (in.past) break;
+        field(have, p, n);
+        have = in.gets(&p, &n);
+        field(have, p, n);
+        if (!in.gets(&p, &n)) refuse(path, "the file ends inside a record");
+        text.append("+\n");
+        have = in.gets(&p, &n);
+        field(have, p, n);
+        if (text.size() >= kFlush) {
+            if (!add_chunk(ctx, text.data(), text.size(), false, records)) refuse(path, "records too short for the device's line index");
+            text.clear();
+        }
+    }
+    if (!add_chunk(ctx, text.data(), text.size(), true, records)) refuse(path, "records too short for the device's line index");
+}
+
+int main(int argc, char *argv[])
+{
+    bind_before_runtime();
+    const char *infile = "-", *outfile = "-";
+    int by_name = 0, by_seq = 0;
+    if (argc < 2) usage(argv[0]);
+    int opt;
+    while ((opt = getopt(argc, argv, "i:o:nsh?")) != -1) {
+        switch (opt) {
+        case 'i': infile = optarg; break;
+        case 'o': outfile = optarg; break;
+        case 'n': by_name = 1, by_seq = 0; break;
+        case 's': by_name = 0, by_seq = 1; break;
+        case '?':
+        case 'h': usage(argv[0]); break;
+        default: fprintf(stderr, "error parameter!\n"); break;
+        }
+    }
+    if (!by_name && !by_seq) by_seq = 1;
+    const bool is_stdin = strncmp(infile, "-", 1) == 0 || !strcmp(infile, "");
+    hpn_ctx *ctx = open_tool_ctx();
+    int rc;
+    const long long begin = usec();
+
+    std::string mem;
+    uint64_t records = 0;
+    bool done = false;
+    if (is_stdin && !slurp_stream(infile, mem)) refuse(infile, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+    if (text_path_enabled()) {
+        if ((rc = hpn_twobit_pack_begin(ctx, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_twobit_pack_begin");
+        if (is_stdin) {
+            const uint64_t piece = text_chunk_bytes();
+            uint64_t at = 0;
+            do {
+                const uint64_t k = mem.size() - at < piece ? mem.size() - at : piece;
+                done = add_chunk(ctx, mem.data() + at, k, at + k == mem.size(), &records);
+                at += k;
+            } while (done && at < mem.size());
+        } else {
+            done = device_feed(ctx, infile, &records);
+        }
+    }
+    if (!done) {
+        if (!is_stdin && !slurp_stream(infile, mem)) refuse(infile, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+        records = 0;
+        if ((rc = hpn_twobit_pack_begin(ctx, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_twobit_pack_begin");
+        host_feed(ctx, infile, mem, &records);
+    }
+    const long long fed = usec();
+    static hpn_twobit_result res;
+    rc = hpn_twobit_pack_finish(ctx, &res);
+    if (rc == HPN_E_DOMAIN && res.bad_record >= 0) {
+        fprintf(stderr, "fastq2twobit: %s: sequence byte of 0x80 or more in record %lld (the reference has no answer there)\n", infile, (long long)res.bad_record);
+        leave(2);
+    }
+    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_twobit_pack_finish");
+    const long long packed = usec();
+    fprintf(stderr, "name: %d\tseq: %d\n", by_name, by_seq);
+    fprintf(stderr, "done read file at %.3f s\nlist count: %d\n", (double)(fed - begin) / CLOCKS_PER_SEC, (int)res.n_records);
+    fprintf(stderr, "done dump_array at %.3f s\n", (double)(packed - begin) / CLOCKS_PER_SEC);
+    fprintf(stderr, "done sort file at %.3f s\n", (double)(packed - begin) / CLOCKS_PER_SEC);
+    write_device_output(ctx, "fastq2twobit", outfile, by_name ? "_sort_by_name.fq" : "_sort_by_seq.fq", res.out_bytes, text_slice_bytes((uint64_t)32 << 20),
+                        [&](uint64_t at, void *buf, uint64_t cap, uint64_t *got) {
+                            const int wrc = hpn_twobit_pack_write(ctx, at, buf, cap, got);
+                            if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_twobit_pack_write");
+                        });
+    if (getenv("HPN_TIMING"))
+        fprintf(stderr, "[hpn] twobit pack: reading and framing %.3f s, packing %.3f s, writing %.3f s; %llu bytes\n", (double)(fed - begin) / 1e6,
+                (double)(packed - fed) / 1e6, (double)(usec() - packed) / 1e6, (unsigned long long)res.out_bytes);
+    fprintf(stderr, "done write file at %.3f s\n", (double)(usec() - begin) / CLOCKS_PER_SEC);
+    fprintf(stderr, "done free list at %.3f s\n", (double)(usec() - begin) / CLOCKS_PER_SEC);
+    quick_exit_ok();
+}

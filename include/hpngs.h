@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 5
+#define HPN_ABI_VERSION 6
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -471,6 +471,46 @@ int hpn_fastq_sort_begin(hpn_ctx *ctx, int by_name, uint64_t max_bytes);
 int hpn_fastq_sort_add(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
 int hpn_fastq_sort_finish(hpn_ctx *ctx, hpn_sort_result *result);
 int hpn_fastq_sort_write(hpn_ctx *ctx, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
+
+/* ---- fastq2twobit.c / twoBit2seq.c: the sequences packed to 2 bits per base, and back -----------------------
+ * fastq2twobit frames a stream as readNextNode frames it (see above), pushes every record on the front of a list and dumps
+ * the list from its head: its output holds the records in REVERSE input order.  A 2-byte header -- (uint8_t)strlen and
+ * (uint8_t)packed length of the input's LAST record -- is followed, per record, by (len + 3) >> 2 bytes: four bases per byte,
+ * the first in the top bits; 'C'/'c' 1, 'A'/'a' 2, 'G'/'g' 3, every other byte ('T', 'U', 'N', '\r', ...) 0; the tail of a
+ * record's last byte is 0; an empty sequence contributes nothing; no record, no byte.  A sequence byte of 0x80 or more indexes
+ * the reference's table with a negative number: there is no answer.
+ *
+ *   hpn_twobit_pack_begin   opens a session (closing the context's earlier one).  max_bytes: as for hpn_fastq_uniq_begin.
+ *   hpn_twobit_pack_add     one chunk, the chunk contract of hpn_fastq_sort_add (the same framing, the same info): irregular
+ *                           text -- HPN_TEXT_NUL, _LONG_LINE, _PARTIAL, _DENSE -- is reported in info->irregular and closes the
+ *                           session.  HPN_E_CAPACITY and HPN_E_DOMAIN (2^31 or more records) as there.
+ *   hpn_twobit_pack_finish  after the last chunk: packs on the device, fills *result.  A sequence byte >= 0x80: HPN_E_DOMAIN,
+ *                           result->bad_record is the smallest 0-based ordinal of such a record and the session is closed.
+ *   hpn_twobit_pack_write   copies up to `cap` bytes of the output (result->out_bytes in all), from byte `offset` on, to `out`
+ *                           (host or device).
+ *
+ * twoBit2seq reads the header and then records of packedLen bytes into a zeroed buffer; of each it prints seqlen characters
+ * (0 'T', 1 'C', 2 'A', 3 'G') and '\n'.  Record bytes behind packedLen read as 0: with packedLen < (seqlen + 3) >> 2 the missing
+ * bases are 'T', a larger packedLen skips the surplus.
+ *
+ *   hpn_twobit_unpack       stateless: n_records records of packed_len bytes at `packed` become n_records * (seq_len + 1) bytes
+ *                           at `out` (host or device pointers, each on its own); *out_bytes tells how many.  seq_len and
+ *                           packed_len are at most 255 (the header's bytes), else HPN_E_ARG.  packed_len == 0 with
+ *                           n_records > 0 is HPN_E_ARG (the reference never ends there).  An out_cap below the size needed is
+ *                           HPN_E_CAPACITY: *out_bytes holds that size and nothing is written. */
+typedef struct hpn_twobit_result {
+    uint64_t n_records;  /* records packed */
+    uint64_t out_bytes;  /* bytes of the output: 0 without records, else 2 + the packed bytes */
+    int64_t bad_record;  /* -1, or with HPN_E_DOMAIN the smallest ordinal of a record with a sequence byte >= 0x80 */
+    uint32_t seq_len;    /* the header's two bytes (0 without records): the last record's length ... */
+    uint32_t packed_len; /* ... and its packed length, both modulo 256 */
+} hpn_twobit_result;
+int hpn_twobit_pack_begin(hpn_ctx *ctx, uint64_t max_bytes);
+int hpn_twobit_pack_add(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
+int hpn_twobit_pack_finish(hpn_ctx *ctx, hpn_twobit_result *result);
+int hpn_twobit_pack_write(hpn_ctx *ctx, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
+int hpn_twobit_unpack(hpn_ctx *ctx, uint32_t seq_len, uint32_t packed_len, const void *packed, uint64_t n_records, void *out, uint64_t out_cap,
+                      uint64_t *out_bytes);
 
 /* ---- ONE text stream framed by several contexts (one per GPU): pieces ----------------------------
  * Record-block sharding of a single FASTQ input (the reference's parallelism stops at
