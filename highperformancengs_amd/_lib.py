@@ -91,6 +91,11 @@ class TwobitResult(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64), ("bad_record", C.c_int64), ("seq_len", C.c_uint32), ("packed_len", C.c_uint32)]
 
 
+class PairResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64 * 2), ("n_pairs", C.c_uint64), ("n_single", C.c_uint64 * 2), ("out_bytes", C.c_uint64 * 4),
+                ("fail_record", C.c_int64), ("fail_mate", C.c_uint32), ("route", C.c_uint32), ("unverified", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TextPiece(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -191,6 +196,10 @@ SYMBOLS = [
     ("hpn_twobit_pack_finish", _int, [_vp, C.POINTER(TwobitResult)]),
     ("hpn_twobit_pack_write", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_twobit_unpack", _int, [_vp, _u32, _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_fastq_pair_begin", _int, [_vp, _u64]),
+    ("hpn_fastq_pair_add", _int, [_vp, _int, _vp, _u64, _int, C.POINTER(SortInfo)]),
+    ("hpn_fastq_pair_finish", _int, [_vp, C.POINTER(PairResult)]),
+    ("hpn_fastq_pair_write", _int, [_vp, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_fastq_text_piece_lines", _int, [_vp, _vp, _u64, _u32, _u64, _int, C.POINTER(TextPiece)]),
     ("hpn_fastq_text_piece_count", _int, [_vp, _u64, _u32, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_piece_trim", _int, [_vp, _u64, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
@@ -252,7 +261,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 6:
+    if L.hpn_abi_version() != 7:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

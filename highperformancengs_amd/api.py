@@ -408,6 +408,38 @@ class Context:
                                           C.byref(got)), "hpn_twobit_unpack")
         return got.value
 
+    # ---- two files split into pairs and singles (pick_pair) ------------------------------------
+    def fastq_pair_begin(self, max_bytes=0):
+        self._ck(self.L.hpn_fastq_pair_begin(self.h, int(max_bytes)), "hpn_fastq_pair_begin")
+
+    def fastq_pair_add(self, mate, chunk, last=False):
+        """One chunk of READ1 (mate 0) or READ2 (mate 1) into that mate's device store; returns the hpn_sort_info."""
+        chunk, n = self._text(chunk)
+        info = _lib.SortInfo()
+        self._ck(self.L.hpn_fastq_pair_add(self.h, int(mate), _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_fastq_pair_add")
+        return info
+
+    def fastq_pair_finish(self):
+        """The hpn_pair_result.  Where neither proposal verifies (HPN_E_DOMAIN) the result comes back with unverified set instead
+        of an exception: there is no output then."""
+        res = _lib.PairResult()
+        rc = self.L.hpn_fastq_pair_finish(self.h, C.byref(res))
+        if not (rc == _lib.E_DOMAIN and res.unverified):
+            self._ck(rc, "hpn_fastq_pair_finish")
+        return res
+
+    def fastq_pair_output(self, which, slice_bytes=1 << 24):
+        """One of the four outputs (0 _1_PE, 1 _1_SE, 2 _2_PE, 3 _2_SE), fetched in slices (hpn_fastq_pair_write)."""
+        parts, at = [], 0
+        buf = np.zeros(max(int(slice_bytes), 1), np.uint8)
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_fastq_pair_write(self.h, int(which), at, _ptr(buf), buf.size, C.byref(got)), "hpn_fastq_pair_write")
+            if not got.value:
+                return b"".join(parts)
+            parts.append(buf[:got.value].tobytes())
+            at += got.value
+
     def sort_pairs(self, keys, vals):
         """Stable ascending sort of uint64 keys with their uint32 payload on the device (hpn_sort_pairs_u64); returns copies."""
         keys, vals = np.array(keys, np.uint64), np.array(vals, np.uint32)

@@ -15,6 +15,7 @@ struct hpn_sort_state;   // hpn_sort.hip
 struct hpn_uniqq_state;  // hpn_uniqq.hip
 struct hpn_usort_state;  // hpn_usort.hip
 struct hpn_twobit_state; // hpn_twobit.hip
+struct hpn_pair_state;   // hpn_pair.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -99,6 +100,7 @@ struct hpn_ctx {
     hpn_uniqq_state *qq = nullptr;  // hpn_fastq_uniqq_*: a uniq session of its own and the members' placement
     hpn_usort_state *us = nullptr;  // hpn_fastq_usort_*: a uniq session of its own, the 64-bit djb2 and the count order
     hpn_twobit_state *tb = nullptr; // hpn_twobit_pack_*: the store, the sizes and offsets, the packed output
+    hpn_pair_state *pr = nullptr;   // hpn_fastq_pair_*: a store per mate, the pairing and its certificate, the four outputs
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -130,6 +132,7 @@ void sort_release(hpn_ctx *c);   // hpn_sort.hip
 void uniqq_release(hpn_ctx *c);  // hpn_uniqq.hip
 void usort_release(hpn_ctx *c);  // hpn_usort.hip
 void twobit_release(hpn_ctx *c); // hpn_twobit.hip
+void pair_release(hpn_ctx *c);   // hpn_pair.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 6
+#define HPN_ABI_VERSION 7
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -511,6 +511,55 @@ int hpn_twobit_pack_finish(hpn_ctx *ctx, hpn_twobit_result *result);
 int hpn_twobit_pack_write(hpn_ctx *ctx, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
 int hpn_twobit_unpack(hpn_ctx *ctx, uint32_t seq_len, uint32_t packed_len, const void *packed, uint64_t n_records, void *out, uint64_t out_cap,
                       uint64_t *out_bytes);
+
+/* ---- pick_pair.c: two FASTQ files split into the reads that still have a mate and those that do not ----------
+ * pick_pair frames both streams as readNextNode frames them (see above; here the quality line KEEPS its line end, so a last line
+ * without '\n' goes out without one) and walks them against each other with c(a, b) = strncmp(a.name, b.name, k), k the offset
+ * of the first space in A's name (a name without one is compared whole):
+ *     loop: a = next(A); b = next(B)
+ *           while a && c(a, b) < 0:  a -> 1_SE; a = next(A)
+ *           while b && c(a, b) > 0:  b -> 2_SE; b = next(B)
+ *           if !a && !b: stop
+ *           a -> 1_PE; b -> 2_PE
+ * An output record is "name\nsequence\n+\nquality line".  The walk is no clean merge-join (each while runs once per round, so it
+ * can pair different names), and it dereferences a NULL record when one file runs out in front of the other.  The device does
+ * not walk: it PROPOSES a pairing and VERIFIES, record by record, that the walk produces exactly that one
+ * (docs/kernels/fastq_pair.md) -- first the identity, when both files hold the same number of records, then a join that takes
+ * file B for ascending.  What verifies is exact for any input, sorted or not; what does not is left to the caller.
+ *
+ *   hpn_fastq_pair_begin   opens a session (closing the context's earlier one).  max_bytes: as for hpn_fastq_uniq_begin, both
+ *                          mates' text together.
+ *   hpn_fastq_pair_add     one chunk of mate 0 (READ1) or 1 (READ2), the chunk contract of hpn_fastq_sort_add (the same framing,
+ *                          the same info); the mates may be fed in any interleaving.  Irregular text -- HPN_TEXT_NUL, _LONG_LINE,
+ *                          _PARTIAL, _DENSE -- is reported in info->irregular and closes the session.  HPN_E_CAPACITY and
+ *                          HPN_E_DOMAIN (2^31 or more records) as there.
+ *   hpn_fastq_pair_finish  after both mates' last chunks: proposes, verifies, writes the four texts on the device, fills
+ *                          *result.  When neither proposal verifies: HPN_E_DOMAIN, result->unverified is 1, fail_mate and
+ *                          fail_record name the first record of the join's proposal that the walk treats otherwise, there are no
+ *                          outputs and the session is closed -- the device has no answer, the reference may have one.
+ *   hpn_fastq_pair_write   copies up to `cap` bytes of output `which_output` (HPN_PAIR_OUT_*; result->out_bytes[which_output]
+ *                          in all), from byte `offset` on, to `out` (host or device). */
+#define HPN_PAIR_IDENTITY 0u /* route: record i of READ1 with record i of READ2 */
+#define HPN_PAIR_JOIN 1u     /* route: the join over an ascending READ2 */
+#define HPN_PAIR_OUT_1_PE 0
+#define HPN_PAIR_OUT_1_SE 1
+#define HPN_PAIR_OUT_2_PE 2
+#define HPN_PAIR_OUT_2_SE 3
+typedef struct hpn_pair_result {
+    uint64_t n_records[2]; /* records of READ1, READ2 */
+    uint64_t n_pairs;      /* records in _1_PE (and in _2_PE) */
+    uint64_t n_single[2];  /* records in _1_SE, _2_SE */
+    uint64_t out_bytes[4]; /* bytes of _1_PE, _1_SE, _2_PE, _2_SE */
+    int64_t fail_record;   /* -1, or with unverified the 0-based ordinal of the first record that does not verify ... */
+    uint32_t fail_mate;    /* ... and its file: 0 READ1, 1 READ2 */
+    uint32_t route;        /* HPN_PAIR_IDENTITY or HPN_PAIR_JOIN: the proposal that verified (or the last one tried) */
+    uint32_t unverified;   /* 1 with HPN_E_DOMAIN: neither proposal is what the walk produces */
+    uint32_t reserved;
+} hpn_pair_result;
+int hpn_fastq_pair_begin(hpn_ctx *ctx, uint64_t max_bytes);
+int hpn_fastq_pair_add(hpn_ctx *ctx, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
+int hpn_fastq_pair_finish(hpn_ctx *ctx, hpn_pair_result *result);
+int hpn_fastq_pair_write(hpn_ctx *ctx, int which_output, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
 
 /* ---- ONE text stream framed by several contexts (one per GPU): pieces ----------------------------
  * Record-block sharding of a single FASTQ input (the reference's parallelism stops at
