@@ -1204,8 +1204,8 @@ constexpr int kFmtThreads = 256, kFmtPer = 2, kFmtSub = kFmtThreads * kFmtPer;  
 #ifndef HPN_BG_SUBS
 #define HPN_BG_SUBS 16
 #endif
-constexpr int kFmtSubs = HPN_BG_SUBS, kFmtTile = kFmtSub * kFmtSubs;   // ... and a workgroup takes 8 such pieces in a row: one chain entry
-                                                             // per 4096 runs (one per 512 was 131 K entries x ~14 ns = 1.9 of 2.0 ms)
+constexpr int kFmtSubs = HPN_BG_SUBS, kFmtTile = kFmtSub * kFmtSubs;   // ... and a workgroup takes HPN_BG_SUBS (16) such pieces in a row: one
+                                                             // chain entry per 8192 runs (one per 512 was 131 K entries x ~14 ns = 1.9 of 2.0 ms)
 // bytes of text a piece may stage (512 lines of up to 78 bytes).  With the kernel's other ~600 bytes this stays within 32 of the
 // CU's LDS granules of 1,280 bytes (scripts/micro/lds_occupancy.hip): four workgroups per CU; 40,960 bytes of text were 33 granules
 // and three.

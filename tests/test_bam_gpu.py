@@ -3,6 +3,7 @@ model and vs the reference bam2depth's golden files.  Bit-exact: integers only."
 import numpy as np
 import pytest
 
+import bedgraph_paths
 import orc
 from bam_synth import fmt_bedgraph, fmt_depth, make_soa
 from conftest import expected, golden_path
@@ -162,6 +163,15 @@ def test_depth_dense_change_points(ctx, W):
     assert rc == 0 and len(wruns) > 80_000 and (np.diff(wruns[100:30_000, 0]) == 1).all()
     assert np.array_equal(runs, wruns)
     assert np.array_equal(win.astype(np.float64), wbins)
+    # the text of these runs -- tens of thousands of neighbours that touch, what taking a line's start digits from the end of the
+    # line before is for -- formatted from the ORACLE's runs: one-layout lines (d), whole words (chr1, chr10)
+    for name in ("d", "chr1", "chr10"):
+        if (name, len(wruns)) not in _DENSE_TEXT:
+            _DENSE_TEXT[(name, len(wruns))] = fmt_bedgraph(name, wruns)
+        bedgraph_paths.check_text(ctx.depth_bedgraph(name), name, wruns, _DENSE_TEXT[(name, len(wruns))])
+
+
+_DENSE_TEXT = {}                                        # (the same runs for every W: formatted once)
 
 
 def test_depth_batches_overlap_and_mix_sorted_with_unsorted(ctx):

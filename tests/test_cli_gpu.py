@@ -528,6 +528,38 @@ def test_bam2depth_requires_index(tmp_path):
     assert p.returncode == 1 and b"BAM indexing file is not available" in p.stderr
 
 
+def test_bam2depth_text_under_real_chromosome_names(tmp_path):
+    """A BAM with contigs chr1, chr10 and a name of 50 characters whose coverage crosses 10^5 and holds one stack 10000 deep: the
+    text formatted on the device (default), the one formatted on the host from the runs (HPN_BEDGRAPH_HOST=1) and the oracle's are
+    the same bytes -- and those of the runs the records were made from."""
+    import bedgraph_paths as BP
+    deep = np.concatenate([BP.hill(), BP.hill(), BP.hill()])
+    deep[51] = 10000
+    per_target = [("chr1", 300_000, BP.lay(99_900, deep, gaps={40: 2})[0]),                 # (line 97 ends at 10^5)
+                  ("chr10", 300_000, BP.lay(99_990, BP.flat(5, 300))[0]),
+                  ("HLA-" + "x" * 46, 5_000, BP.lay(0, BP.flat(1, 200), lens=3)[0])]
+    refs = [(name, tlen) for name, tlen, _ in per_target]
+    recs = []
+    for tid, (_, _, runs) in enumerate(per_target):
+        for k, (p, ln) in enumerate(zip(*BP.records_for_runs(runs))):
+            recs.append(bamio.BamRecord(tid=tid, pos=int(p), flag=0, cigar=[int(ln) << 4], seq="ACGT", name="r%d" % k))
+    src = tmp_path / "src"
+    src.mkdir()
+    assert bamio.write_bam(str(src / "x.bam"), refs, recs) == len(recs) > 10000
+    designed = b"".join(BP.fmt_text(name, BP.as_runs(runs)) for name, _, runs in per_target)
+    assert b"chr1\t99999\t100000\t" in designed and b"\t10000\n" in designed
+    bed, dep, _, _ = orc.bam2depth_text(bamio.read_bam_records(str(src / "x.bam")), 20000)
+    assert bed == designed
+    for sub, env in (("dev", {}), ("host", {"HPN_BEDGRAPH_HOST": "1"})):
+        d = tmp_path / sub
+        d.mkdir()
+        p, files = _run("bam2depth", ["-o", "d", "x.bam"], [str(src / "x.bam")], d, env)
+        assert p.returncode == 0, p.stderr.decode()
+        assert files == ["d.1.depth", "x.bam.1.bedGraph"]
+        assert open(d / "x.bam.1.bedGraph", "rb").read() == bed, sub
+        assert open(d / "d.1.depth", "rb").read() == dep, sub
+
+
 @pytest.mark.parametrize("case,why", [("count_badcrc", b"CRC-32 mismatch"), ("count_badcrc_mid", b"CRC-32 mismatch in a member"),
                                       ("count_badisize", b"ISIZE mismatch")])
 def test_gzip_on_the_gpu_checks_every_member_like_gzread(manifest, case, why, tmp_path):
