@@ -160,6 +160,14 @@ class Context:
         self._ck(self.L.hpn_fastq_trim_dev(self.h, _ptr(d_seq), _ptr(d_qual), _ptr(d_off), n, S, E, _ptr(d_out_seq),
                                            _ptr(d_out_qual), _ptr(d_out_off)), "hpn_fastq_trim_dev")
 
+    def fastq_trim_points_dev(self, d_seq, d_qual, d_off, n, d_beg, d_end, d_out_seq, d_out_qual, d_out_off):
+        self._ck(self.L.hpn_fastq_trim_points_dev(self.h, _ptr(d_seq), _ptr(d_qual), _ptr(d_off), n, _ptr(d_beg), _ptr(d_end),
+                                                  _ptr(d_out_seq), _ptr(d_out_qual), _ptr(d_out_off)), "hpn_fastq_trim_points_dev")
+
+    def fastq_qtrim_points_dev(self, d_qual, d_off, n, threshold, d_beg, d_end):
+        self._ck(self.L.hpn_fastq_qtrim_points_dev(self.h, _ptr(d_qual), _ptr(d_off), n, threshold, _ptr(d_beg), _ptr(d_end)),
+                 "hpn_fastq_qtrim_points_dev")
+
     # ---- extension: quality-threshold trim points --------------------------
     def fastq_qtrim_points(self, qual, off, threshold):
         qual = np.ascontiguousarray(qual, np.uint8)
