@@ -6,17 +6,10 @@
 // the same number of records, else (or when that does not verify) the join -- and verifies it against the reference's walk
 // record by record; a pairing that verifies is written out as four flat texts.  When neither does, the device has no answer:
 // HPN_E_DOMAIN with result->unverified, and the caller walks the files as the reference does.
-#include <string.h>
-
 #include "hpn_store.hpp"
+#include "kernels/sort_desc.hpp"
 
 namespace hpn {
-// kernels/fastq_sort.hip
-hipError_t launch_sort_frame(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st);
-// kernels/fastq_uniq.hip
-hipError_t uniq_scan64(const uint32_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
-uint64_t uniq_scan_tiles(uint64_t n);
 // kernels/fastq_pair.hip
 hipError_t launch_pair_klen(const uint8_t *d_text, const void *d_desc, uint32_t n, uint32_t *d_klen, hipStream_t st);
 hipError_t launch_pair_identity(uint32_t n, uint32_t *d_m, hipStream_t st);
@@ -36,16 +29,12 @@ hipError_t launch_pair_write(const uint8_t *d_text, const void *d_desc, const ui
 using namespace hpn;
 
 namespace {
-constexpr size_t kDescBytes = 16;                                       // kernels/fastq_sort.hip: SortDesc
-enum { kPrTicket = 0, kPrErr = 1, kPrFail = 2, kPrWords = 4 };          // the device's info block (uint32 words)
+enum { kPrFail = kInfoOwn };   // the family's word of the info block
 }  // namespace
 
 struct hpn_pair_state {
-    uint64_t limit = 0;
-    bool open = false, finished = false;
-    RecordStore m[2];
+    StoreSession s;
     Scratch klen, mate, flag[2], rank[2], pair[2], size[2], off[2], status, out[4];
-    uint32_t *d_info = nullptr, *h_info = nullptr;
     uint64_t out_total[4] = {0, 0, 0, 0};
 };
 
@@ -53,16 +42,12 @@ namespace {
 
 void drop_session(hpn_pair_state *u)
 {
-    store_release(u->m[0]);
-    store_release(u->m[1]);
+    session_drop(u->s);
     Scratch *ss[] = {&u->klen,    &u->mate,    &u->flag[0], &u->flag[1], &u->rank[0], &u->rank[1], &u->pair[0], &u->pair[1], &u->size[0],
                      &u->size[1], &u->off[0],  &u->off[1],  &u->status,  &u->out[0],  &u->out[1],  &u->out[2],  &u->out[3]};
     for (Scratch *s : ss) release_scratch(*s);
-    u->open = u->finished = false;
     for (uint64_t &t : u->out_total) t = 0;
 }
-
-const uint8_t *text_of(const RecordStore &m) { return (const uint8_t *)m.store.p + kStorePad; }
 
 // flags, ranks, the pair list and the one comparison per record over the proposal in u->mate.  *bad: 0xffffffff when the
 // proposal is what the walk produces, else the smallest failing mate << 31 | ordinal.
@@ -73,19 +58,17 @@ int verify(hpn_ctx *c, hpn_pair_state *u, uint32_t nA, uint32_t nB, uint64_t *n_
     const uint32_t n[2] = {nA, nB};
     HPN_HIP(c, launch_pair_flags((const uint32_t *)u->mate.p, nA, nB, fl[0], fl[1], c->stream));
     for (int s = 0; s < 2; ++s) {
-        if (n[s]) HPN_HIP(c, uniq_scan64(fl[s], rk[s], n[s], (u64 *)u->status.p, u->d_info + kPrTicket, u->d_info + kPrErr, c->stream));
+        if (n[s]) HPN_HIP(c, uniq_scan64(fl[s], rk[s], n[s], (u64 *)u->status.p, u->s.ticket(), u->s.err(), c->stream));
         else HPN_HIP(c, hipMemsetAsync(rk[s], 0, 8, c->stream));
     }
     HPN_HIP(c, launch_pair_scatter((const uint32_t *)u->mate.p, rk[0], nA, (uint32_t *)u->pair[0].p, (uint32_t *)u->pair[1].p, c->stream));
-    HPN_HIP(c, launch_pair_verify(text_of(u->m[0]), u->m[0].desc.p, (const uint32_t *)u->klen.p, nA, text_of(u->m[1]), u->m[1].desc.p, nB,
+    HPN_HIP(c, launch_pair_verify(u->s.text(0), u->s.m[0].desc.p, (const uint32_t *)u->klen.p, nA, u->s.text(1), u->s.m[1].desc.p, nB,
                                   (const uint32_t *)u->mate.p, rk[0], fl[1], rk[1], (const uint32_t *)u->pair[0].p, (const uint32_t *)u->pair[1].p,
-                                  u->d_info + kPrFail, c->n_cu, c->stream));
+                                  u->s.d_info + kPrFail, c->n_cu, c->stream));
     HPN_HIP(c, hipMemcpyAsync(n_pairs, rk[0] + nA, 8, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipMemcpyAsync(u->h_info, u->d_info, kPrWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (u->h_info[kPrErr]) return fail(c, HPN_E_HIP, "prefix-scan hand-off timed out");
-    *bad = u->h_info[kPrFail];
-    return HPN_OK;
+    const int rc = info_fetch(c, u->s);
+    *bad = u->s.h_info[kPrFail];
+    return rc;
 }
 
 }  // namespace
@@ -95,8 +78,7 @@ void pair_release(hpn_ctx *c)
 {
     if (!c->pr) return;
     drop_session(c->pr);
-    if (c->pr->d_info) (void)hipFree(c->pr->d_info);
-    if (c->pr->h_info) (void)hipHostFree(c->pr->h_info);
+    info_free(c->pr->s);
     delete c->pr;
     c->pr = nullptr;
 }
@@ -109,63 +91,30 @@ int hpn_fastq_pair_begin(hpn_ctx *c, uint64_t max_bytes)
     if (!c) return HPN_E_ARG;
     HPN_HIP(c, hipSetDevice(c->device));
     if (!c->pr) c->pr = new hpn_pair_state;
-    hpn_pair_state *u = c->pr;
-    if (!u->d_info) {
-        HPN_HIP(c, hipMalloc((void **)&u->d_info, kPrWords * sizeof(uint32_t)));
-        HPN_HIP(c, hipHostMalloc((void **)&u->h_info, kPrWords * sizeof(uint32_t), hipHostMallocDefault));
-    }
-    drop_session(u);
-    if (!max_bytes) {   // half of what is free, as hpn_fastq_sort_begin: the other half is the reserve for the stores' growth and the outputs
-        size_t fr = 0, total = 0;
-        HPN_HIP(c, hipMemGetInfo(&fr, &total));
-        max_bytes = fr / 2;
-    }
-    u->limit = max_bytes;
-    u->open = true;
-    return HPN_OK;
+    drop_session(c->pr);
+    return session_begin(c, c->pr->s, 2, max_bytes);
 }
 
 int hpn_fastq_pair_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_pair_state *u = c->pr;
-    if (!u || !u->open || u->finished) return fail(c, HPN_E_STATE, "hpn_fastq_pair_begin first (or the session was closed by an irregular chunk)");
-    if (mate != 0 && mate != 1) return fail(c, HPN_E_ARG, "mate is %d (0 or 1)", mate);
-    if (nbytes && !text) return fail(c, HPN_E_ARG, "text is NULL");
-    RecordStore &m = u->m[mate];
-    if (m.closed) return fail(c, HPN_E_STATE, "mate %d's stream has had its last chunk", mate);
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    const uint64_t span = m.len - m.pos + nbytes;
-    if (span >= (1ull << 31) - 4096) return fail(c, HPN_E_ARG, "chunk of %llu bytes (limit 2^31 - 4 KiB with the unfinished record)", (unsigned long long)nbytes);
-    const uint64_t held = u->m[0].len + u->m[1].len;
-    if (held + nbytes > u->limit) {
-        u->open = false;
-        return fail(c, HPN_E_CAPACITY, "the stores need %llu bytes, max_bytes is %llu", (unsigned long long)(held + nbytes), (unsigned long long)u->limit);
-    }
-    bool close = false;
-    const int rc = store_add(c, m, kDescBytes, launch_sort_frame, text, nbytes, last, &info->n_records, &info->irregular, &close);
-    info->store_bytes = m.len;
-    if (close) u->open = false;
-    return rc;
+    return session_add(c, c->pr ? &c->pr->s : nullptr, "hpn_fastq_pair", mate, kSortDescBytes, launch_sort_frame, text, nbytes, last, true, info);
 }
 
 int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
     hpn_pair_state *u = c->pr;
-    if (!u || !u->open || u->finished) return fail(c, HPN_E_STATE, "no open hpn_fastq_pair session");
-    if (!u->m[0].closed || !u->m[1].closed) return fail(c, HPN_E_STATE, "both mates' streams need their last chunk first");
-    HPN_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_pair", kSortDescBytes)) != HPN_OK) return rc;
     memset(res, 0, sizeof *res);
     res->fail_record = -1;
-    int rc;
-    const uint32_t nA = (uint32_t)u->m[0].n, nB = (uint32_t)u->m[1].n, n[2] = {nA, nB};
+    const uint32_t nA = (uint32_t)u->s.m[0].n, nB = (uint32_t)u->s.m[1].n, n[2] = {nA, nB};
     const uint32_t big = nA > nB ? nA : nB;
     res->n_records[0] = nA, res->n_records[1] = nB;
     if (!nA && !nB) {   // the walk's first round finds nothing: four empty outputs
         HPN_HIP(c, hipStreamSynchronize(c->stream));
-        u->finished = true;
+        u->s.finished = true;
         return HPN_OK;
     }
     if ((rc = need(c, u->klen, (size_t)nA * 4)) != HPN_OK || (rc = need(c, u->mate, (size_t)nA * 4)) != HPN_OK ||
@@ -175,9 +124,8 @@ int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)
         if ((rc = need(c, u->flag[s], (size_t)n[s] * 4)) != HPN_OK || (rc = need(c, u->rank[s], ((size_t)n[s] + 1) * 8)) != HPN_OK ||
             (rc = need(c, u->pair[s], (size_t)nA * 4)) != HPN_OK)   // (a join may give several A records one mate)
             return rc;
-    HPN_HIP(c, hipMemsetAsync(u->d_info, 0, kPrWords * sizeof(uint32_t), c->stream));
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
-    HPN_HIP(c, launch_pair_klen(text_of(u->m[0]), u->m[0].desc.p, nA, (uint32_t *)u->klen.p, c->stream));
+    HPN_HIP(c, launch_pair_klen(u->s.text(0), u->s.m[0].desc.p, nA, (uint32_t *)u->klen.p, c->stream));
     uint64_t n_pairs = 0;
     uint32_t bad = 0;
     bool ok = false;
@@ -188,7 +136,7 @@ int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)
         res->route = HPN_PAIR_IDENTITY;
     }
     if (!ok) {
-        HPN_HIP(c, launch_pair_find(text_of(u->m[0]), u->m[0].desc.p, (const uint32_t *)u->klen.p, nA, text_of(u->m[1]), u->m[1].desc.p, nB,
+        HPN_HIP(c, launch_pair_find(u->s.text(0), u->s.m[0].desc.p, (const uint32_t *)u->klen.p, nA, u->s.text(1), u->s.m[1].desc.p, nB,
                                     (uint32_t *)u->mate.p, c->n_cu, c->stream));
         if ((rc = verify(c, u, nA, nB, &n_pairs, &bad)) != HPN_OK) return rc;
         ok = bad == 0xffffffffu;
@@ -205,28 +153,22 @@ int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)
         if (!n[s]) continue;
         for (int col = 0; col < 2; ++col)
             if ((rc = need(c, u->size[col], (size_t)big * 4)) != HPN_OK || (rc = need(c, u->off[col], ((size_t)big + 1) * 8)) != HPN_OK) return rc;
-        uint32_t *sz[2] = {(uint32_t *)u->size[0].p, (uint32_t *)u->size[1].p};
-        uint64_t *of[2] = {(uint64_t *)u->off[0].p, (uint64_t *)u->off[1].p};
-        HPN_HIP(c, launch_pair_sizes(u->m[s].desc.p, (const uint32_t *)u->flag[s].p, n[s], sz[0], sz[1], c->stream));
+        const uint64_t *of[2] = {(const uint64_t *)u->off[0].p, (const uint64_t *)u->off[1].p};
+        HPN_HIP(c, launch_pair_sizes(u->s.m[s].desc.p, (const uint32_t *)u->flag[s].p, n[s], (uint32_t *)u->size[0].p, (uint32_t *)u->size[1].p, c->stream));
         uint64_t sum[2] = {0, 0};
-        for (int col = 0; col < 2; ++col) {
-            HPN_HIP(c, uniq_scan64(sz[col], of[col], n[s], (u64 *)u->status.p, u->d_info + kPrTicket, u->d_info + kPrErr, c->stream));
-            HPN_HIP(c, hipMemcpyAsync(&sum[col], of[col] + n[s], 8, hipMemcpyDeviceToHost, c->stream));
-        }
-        HPN_HIP(c, hipStreamSynchronize(c->stream));
+        for (int col = 0; col < 2; ++col)
+            if ((rc = scan_sizes(c, u->s, u->status, u->size[col], u->off[col], n[s], &sum[col])) != HPN_OK) return rc;
         for (int col = 0; col < 2; ++col) {
             if ((rc = need(c, u->out[2 * s + col], sum[col])) != HPN_OK) return rc;
             u->out_total[2 * s + col] = res->out_bytes[2 * s + col] = sum[col];
         }
-        HPN_HIP(c, launch_pair_write(text_of(u->m[s]), u->m[s].desc.p, (const uint32_t *)u->flag[s].p, of[0], of[1], n[s],
+        HPN_HIP(c, launch_pair_write(u->s.text(s), u->s.m[s].desc.p, (const uint32_t *)u->flag[s].p, of[0], of[1], n[s],
                                      (uint8_t *)u->out[2 * s].p, (uint8_t *)u->out[2 * s + 1].p, c->n_cu, c->stream));
     }
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
     c->ev_valid[kFamTrim] = true;
-    HPN_HIP(c, hipMemcpyAsync(u->h_info, u->d_info, kPrWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (u->h_info[kPrErr]) return fail(c, HPN_E_HIP, "prefix-scan hand-off timed out");
-    u->finished = true;
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    u->s.finished = true;
     return HPN_OK;
 }
 
@@ -234,18 +176,10 @@ int hpn_fastq_pair_write(hpn_ctx *c, int which_output, uint64_t offset, void *ou
 {
     if (!c || !written) return HPN_E_ARG;
     hpn_pair_state *u = c->pr;
-    if (!u || !u->finished) return fail(c, HPN_E_STATE, "hpn_fastq_pair_finish first");
+    const int rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_pair", written);
+    if (rc != HPN_OK) return rc;
     if (which_output < 0 || which_output > 3) return fail(c, HPN_E_ARG, "which_output is %d (0 .. 3)", which_output);
-    HPN_HIP(c, hipSetDevice(c->device));
-    *written = 0;
-    const uint64_t total = u->out_total[which_output];
-    if (offset > total) return fail(c, HPN_E_ARG, "offset %llu beyond the output's %llu bytes", (unsigned long long)offset, (unsigned long long)total);
-    const uint64_t k = total - offset < cap ? total - offset : cap;
-    if (k && !out) return fail(c, HPN_E_ARG, "out is NULL");
-    if (k) HPN_HIP(c, hipMemcpyAsync(out, (const uint8_t *)u->out[which_output].p + offset, k, hipMemcpyDefault, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    *written = k;
-    return HPN_OK;
+    return session_write_slice(c, u->out[which_output], u->out_total[which_output], offset, out, cap, written);
 }
 
 }  // extern "C"

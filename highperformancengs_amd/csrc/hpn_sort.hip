@@ -7,9 +7,8 @@
 // next 8 bytes and then by run number -- both sorts stable, both over the digits in which two keys differ and no others -- so
 // that the i-th sorted element goes to the i-th tied position.  A run whose neighbours are all equal behind the bytes sorted
 // so far is settled: duplicates leave after one look, and so does every run whose bytes are used up.
-#include <string.h>
-
 #include "hpn_store.hpp"
+#include "kernels/sort_desc.hpp"
 
 namespace hpn {
 struct SortTied {   // kernels/fastq_sort.hip
@@ -17,8 +16,6 @@ struct SortTied {   // kernels/fastq_sort.hip
     u64 *kp;
 };
 // kernels/fastq_sort.hip
-hipError_t launch_sort_frame(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st);
 hipError_t launch_sort_key0(const uint8_t *d_text, const void *d_desc, int by_name, uint32_t n, uint64_t *d_key, uint32_t *d_val,
                             hipStream_t st);
 hipError_t launch_sort_bits(const uint64_t *d_key, uint32_t n, uint64_t *d_bits, int n_cu, hipStream_t st);
@@ -37,31 +34,20 @@ hipError_t launch_sort_place(const uint32_t *d_val2, const uint32_t *d_val1, con
 hipError_t launch_sort_sizes(const void *d_desc, const uint32_t *d_order, uint32_t n, uint32_t *d_size, hipStream_t st);
 hipError_t launch_sort_write(const uint8_t *d_text, const void *d_desc, const uint32_t *d_order, const uint64_t *d_off, uint32_t n,
                              uint8_t *d_out, int n_cu, hipStream_t st);
-// kernels/fastq_uniq.hip
-hipError_t uniq_scan32(const uint32_t *d_in, uint32_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
-hipError_t uniq_scan64(const uint32_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
-uint64_t uniq_scan_tiles(uint64_t n);
-uint64_t uniq_sort_hist_words(uint32_t n);
-hipError_t uniq_sort_pairs_digits(uint64_t *d_keys, uint32_t *d_vals, uint32_t n, uint32_t digits, uint64_t *d_keys_tmp, uint32_t *d_vals_tmp,
-                                  uint32_t *d_hist, uint32_t *d_offs, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t s);
 }  // namespace hpn
 
 using namespace hpn;
 
 namespace {
-constexpr size_t kDescBytes = 16;       // kernels/fastq_sort.hip: SortDesc
 constexpr uint32_t kFirstBytes = 6, kWordBytes = 8, kMaxRounds = 128;   // 6 + 8 * 127 = 1022, the longest line gzgets leaves whole
-enum { kSiTicket = 0, kSiErr = 1, kSiBits = 2, kSiWords = 8 };          // the device's info block (uint32 words; bits: two uint64)
+enum { kSiBits = kInfoOwn };   // the family's words of the info block: two uint64
 }  // namespace
 
 struct hpn_sort_state {
+    StoreSession s;
     int by_name = 0;
-    uint64_t limit = 0;
-    bool open = false, finished = false;
-    RecordStore m;
     Scratch order, key, val, key_tmp, val_tmp, hist, offs, status, word1, val1, word, head, gid, stay, keep, at, size, off, out;
     Scratch t_pos[2], t_ord[2], t_len[2], t_run[2], t_kp[2];
-    uint32_t *d_info = nullptr, *h_info = nullptr;
     uint32_t N = 0;
     uint64_t out_total = 0;
 };
@@ -70,7 +56,7 @@ namespace {
 
 void drop_session(hpn_sort_state *u)
 {
-    store_release(u->m);
+    session_drop(u->s);
     Scratch *ss[] = {&u->order, &u->key, &u->val, &u->key_tmp, &u->val_tmp, &u->hist, &u->offs, &u->status, &u->word1, &u->val1, &u->word,
                      &u->head, &u->gid, &u->stay, &u->keep, &u->at, &u->size, &u->off, &u->out};
     for (Scratch *s : ss) release_scratch(*s);
@@ -78,26 +64,17 @@ void drop_session(hpn_sort_state *u)
         release_scratch(u->t_pos[k]), release_scratch(u->t_ord[k]), release_scratch(u->t_len[k]);
         release_scratch(u->t_run[k]), release_scratch(u->t_kp[k]);
     }
-    u->open = u->finished = false;
-}
-
-int fetch_info(hpn_ctx *c, hpn_sort_state *u)
-{
-    HPN_HIP(c, hipMemcpyAsync(u->h_info, u->d_info, kSiWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (u->h_info[kSiErr]) return fail(c, HPN_E_HIP, "prefix-scan hand-off timed out");
-    return HPN_OK;
 }
 
 // Stable sort of (key, val) by the digits in which two of the n keys differ, interior constant digits left out as well.
 int sort_differing(hpn_ctx *c, hpn_sort_state *u, uint32_t n)
 {
     int rc;
-    uint64_t *bits = (uint64_t *)(u->d_info + kSiBits);
+    uint64_t *bits = (uint64_t *)(u->s.d_info + kSiBits);
     HPN_HIP(c, launch_sort_bits((const uint64_t *)u->key.p, n, bits, c->n_cu, c->stream));
-    if ((rc = fetch_info(c, u)) != HPN_OK) return rc;
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
     uint64_t h[2];
-    memcpy(h, u->h_info + kSiBits, sizeof h);
+    memcpy(h, u->s.h_info + kSiBits, sizeof h);
     const uint64_t differ = n ? h[0] ^ h[1] : 0;
     uint32_t digits = 0;
     for (int d = 0; d < 8; ++d)
@@ -109,7 +86,7 @@ int sort_differing(hpn_ctx *c, hpn_sort_state *u, uint32_t n)
         (rc = need(c, u->status, uniq_scan_tiles(hw > n ? hw : n) * 8)) != HPN_OK)
         return rc;
     HPN_HIP(c, uniq_sort_pairs_digits((uint64_t *)u->key.p, (uint32_t *)u->val.p, n, digits, (uint64_t *)u->key_tmp.p, (uint32_t *)u->val_tmp.p,
-                                      (uint32_t *)u->hist.p, (uint32_t *)u->offs.p, (u64 *)u->status.p, u->d_info + kSiTicket, u->d_info + kSiErr,
+                                      (uint32_t *)u->hist.p, (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.ticket(), u->s.err(),
                                       c->stream));
     return HPN_OK;
 }
@@ -126,7 +103,7 @@ int settle(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, int cur, const ui
     int rc;
     if ((rc = need(c, u->status, uniq_scan_tiles(m) * 8)) != HPN_OK) return rc;
     uint32_t *head = (uint32_t *)u->head.p, *gid = (uint32_t *)u->gid.p, *stay = (uint32_t *)u->stay.p, *keep = (uint32_t *)u->keep.p;
-    uint32_t *at = (uint32_t *)u->at.p, *ticket = u->d_info + kSiTicket, *err = u->d_info + kSiErr;
+    uint32_t *at = (uint32_t *)u->at.p, *ticket = u->s.ticket(), *err = u->s.err();
     const SortTied a = tied(u, cur), b = tied(u, cur ^ 1);
     HPN_HIP(c, launch_sort_heads(word, a.run, m, head, c->stream));
     HPN_HIP(c, uniq_scan32(head, gid, m, (u64 *)u->status.p, ticket, err, c->stream));
@@ -134,7 +111,7 @@ int settle(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, int cur, const ui
     HPN_HIP(c, uniq_scan32(keep, at, m, (u64 *)u->status.p, ticket, err, c->stream));
     uint32_t n_left = 0;
     HPN_HIP(c, hipMemcpyAsync(&n_left, at + m, 4, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = fetch_info(c, u)) != HPN_OK) return rc;
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
     if (n_left) HPN_HIP(c, launch_sort_compact(keep, at, head, gid, a, m, b, c->stream));
     *left = n_left;
     return HPN_OK;
@@ -144,7 +121,7 @@ int order_records(hpn_ctx *c, hpn_sort_state *u, hpn_sort_result *res)
 {
     int rc;
     const uint32_t N = u->N;
-    const uint8_t *text = (const uint8_t *)u->m.store.p + kStorePad;
+    const uint8_t *text = u->s.text(0);
     if ((rc = need(c, u->order, (size_t)N * 4)) != HPN_OK) return rc;
     if (!N) return HPN_OK;
     Scratch *per4[] = {&u->val, &u->val1, &u->head, &u->stay, &u->keep, &u->t_pos[0], &u->t_pos[1], &u->t_ord[0], &u->t_ord[1],
@@ -160,9 +137,9 @@ int order_records(hpn_ctx *c, hpn_sort_state *u, hpn_sort_result *res)
     // round 0
     int cur = 0;
     uint32_t m = 0, consumed = kFirstBytes;
-    HPN_HIP(c, launch_sort_key0(text, u->m.desc.p, u->by_name, N, key, val, c->stream));
+    HPN_HIP(c, launch_sort_key0(text, u->s.m[0].desc.p, u->by_name, N, key, val, c->stream));
     if ((rc = sort_differing(c, u, N)) != HPN_OK) return rc;
-    HPN_HIP(c, launch_sort_place0(u->m.desc.p, u->by_name, val, N, order, tied(u, cur), c->stream));
+    HPN_HIP(c, launch_sort_place0(u->s.m[0].desc.p, u->by_name, val, N, order, tied(u, cur), c->stream));
     if ((rc = settle(c, u, text, cur, key, consumed, N, &m)) != HPN_OK) return rc;
     res->rounds = 1;
     while (m) {
@@ -191,8 +168,7 @@ void sort_release(hpn_ctx *c)
 {
     if (!c->sq) return;
     drop_session(c->sq);
-    if (c->sq->d_info) (void)hipFree(c->sq->d_info);
-    if (c->sq->h_info) (void)hipHostFree(c->sq->h_info);
+    info_free(c->sq->s);
     delete c->sq;
     c->sq = nullptr;
 }
@@ -205,91 +181,51 @@ int hpn_fastq_sort_begin(hpn_ctx *c, int by_name, uint64_t max_bytes)
     if (!c) return HPN_E_ARG;
     HPN_HIP(c, hipSetDevice(c->device));
     if (!c->sq) c->sq = new hpn_sort_state;
-    hpn_sort_state *u = c->sq;
-    if (!u->d_info) {
-        HPN_HIP(c, hipMalloc((void **)&u->d_info, kSiWords * sizeof(uint32_t)));
-        HPN_HIP(c, hipHostMalloc((void **)&u->h_info, kSiWords * sizeof(uint32_t), hipHostMallocDefault));
-    }
-    drop_session(u);
-    if (!max_bytes) {   // half of what is free: the other half is the reserve for the store's growth, the sorts' arrays and the output
-        size_t fr = 0, total = 0;
-        HPN_HIP(c, hipMemGetInfo(&fr, &total));
-        max_bytes = fr / 2;
-    }
-    u->by_name = by_name ? 1 : 0, u->limit = max_bytes;
-    u->open = true;
-    return HPN_OK;
+    drop_session(c->sq);
+    c->sq->by_name = by_name ? 1 : 0;
+    return session_begin(c, c->sq->s, 1, max_bytes);
 }
 
 int hpn_fastq_sort_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_sort_state *u = c->sq;
-    if (!u || !u->open || u->finished) return fail(c, HPN_E_STATE, "hpn_fastq_sort_begin first (or the session was closed by an irregular chunk)");
-    if (nbytes && !text) return fail(c, HPN_E_ARG, "text is NULL");
-    RecordStore &m = u->m;
-    if (m.closed) return fail(c, HPN_E_STATE, "the stream has had its last chunk");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    const uint64_t span = m.len - m.pos + nbytes;
-    if (span >= (1ull << 31) - 4096) return fail(c, HPN_E_ARG, "chunk of %llu bytes (limit 2^31 - 4 KiB with the unfinished record)", (unsigned long long)nbytes);
-    if (m.len + nbytes > u->limit) {
-        u->open = false;
-        return fail(c, HPN_E_CAPACITY, "the store needs %llu bytes, max_bytes is %llu", (unsigned long long)(m.len + nbytes), (unsigned long long)u->limit);
-    }
-    bool close = false;
-    const int rc = store_add(c, m, kDescBytes, launch_sort_frame, text, nbytes, last, &info->n_records, &info->irregular, &close);
-    info->store_bytes = m.len;
-    if (close) u->open = false;
-    return rc;
+    return session_add(c, c->sq ? &c->sq->s : nullptr, "hpn_fastq_sort", 0, kSortDescBytes, launch_sort_frame, text, nbytes, last, false, info);
 }
 
 int hpn_fastq_sort_finish(hpn_ctx *c, hpn_sort_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
     hpn_sort_state *u = c->sq;
-    if (!u || !u->open || u->finished) return fail(c, HPN_E_STATE, "no open hpn_fastq_sort session");
-    if (!u->m.closed) return fail(c, HPN_E_STATE, "the stream needs its last chunk first");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(res, 0, sizeof *res);
     int rc;
-    if ((rc = grow_keep(c, u->m.store, 2 * kStorePad, 0)) != HPN_OK || (rc = grow_keep(c, u->m.desc, kDescBytes, 0)) != HPN_OK) return rc;   // (a stream without a byte has no buffers yet)
-    HPN_HIP(c, hipMemsetAsync(u->d_info, 0, kSiWords * sizeof(uint32_t), c->stream));
-    const uint32_t N = u->N = (uint32_t)u->m.n;
+    if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_sort", kSortDescBytes)) != HPN_OK) return rc;
+    memset(res, 0, sizeof *res);
+    const uint32_t N = u->N = (uint32_t)u->s.m[0].n;
     res->n_records = N;
     uint64_t framed = 0;   // where the last record ends (a last line without '\n': behind the byte it lost)
     if (N) {
-        struct {
-            uint64_t off;
-            uint16_t nlen, slen, qlen, qrel;
-        } d;   // SortDesc as the host reads it
-        static_assert(sizeof d == kDescBytes, "SortDesc layout");
-        HPN_HIP(c, hipMemcpy(&d, (const uint8_t *)u->m.desc.p + (size_t)(N - 1) * kDescBytes, kDescBytes, hipMemcpyDeviceToHost));
+        SortDesc d;
+        HPN_HIP(c, hipMemcpy(&d, (const SortDesc *)u->s.m[0].desc.p + (N - 1), sizeof d, hipMemcpyDeviceToHost));
         framed = d.off + d.qrel + d.qlen + 1u;
     }
-    res->lone_line = framed < u->m.len ? 1u : 0u;
+    res->lone_line = framed < u->s.m[0].len ? 1u : 0u;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTally], c->stream));
     if ((rc = order_records(c, u, res)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTally], c->stream));
     c->ev_valid[kFamTally] = true;
     // the output text
-    if ((rc = need(c, u->size, (size_t)N * 4)) != HPN_OK || (rc = need(c, u->off, ((size_t)N + 1) * 8)) != HPN_OK ||
-        (rc = need(c, u->status, uniq_scan_tiles(N) * 8)) != HPN_OK)
-        return rc;
-    HPN_HIP(c, launch_sort_sizes(u->m.desc.p, (const uint32_t *)u->order.p, N, (uint32_t *)u->size.p, c->stream));
-    HPN_HIP(c, uniq_scan64((const uint32_t *)u->size.p, (uint64_t *)u->off.p, N, (u64 *)u->status.p, u->d_info + kSiTicket, u->d_info + kSiErr, c->stream));
+    if ((rc = need(c, u->size, (size_t)N * 4)) != HPN_OK || (rc = need(c, u->off, ((size_t)N + 1) * 8)) != HPN_OK) return rc;
+    HPN_HIP(c, launch_sort_sizes(u->s.m[0].desc.p, (const uint32_t *)u->order.p, N, (uint32_t *)u->size.p, c->stream));
     uint64_t total = 0;
-    HPN_HIP(c, hipMemcpyAsync(&total, (const uint64_t *)u->off.p + N, 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = fetch_info(c, u)) != HPN_OK) return rc;
+    if ((rc = scan_sizes(c, u->s, u->status, u->size, u->off, N, &total)) != HPN_OK) return rc;
     if ((rc = need(c, u->out, total)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
-    HPN_HIP(c, launch_sort_write((const uint8_t *)u->m.store.p + kStorePad, u->m.desc.p, (const uint32_t *)u->order.p, (const uint64_t *)u->off.p, N,
+    HPN_HIP(c, launch_sort_write(u->s.text(0), u->s.m[0].desc.p, (const uint32_t *)u->order.p, (const uint64_t *)u->off.p, N,
                                  (uint8_t *)u->out.p, c->n_cu, c->stream));
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
     c->ev_valid[kFamTrim] = true;
     HPN_HIP(c, hipStreamSynchronize(c->stream));
     u->out_total = res->out_bytes = total;
-    u->finished = true;
+    u->s.finished = true;
     return HPN_OK;
 }
 
@@ -297,16 +233,8 @@ int hpn_fastq_sort_write(hpn_ctx *c, uint64_t offset, void *out, uint64_t cap, u
 {
     if (!c || !written) return HPN_E_ARG;
     hpn_sort_state *u = c->sq;
-    if (!u || !u->finished) return fail(c, HPN_E_STATE, "hpn_fastq_sort_finish first");
-    HPN_HIP(c, hipSetDevice(c->device));
-    *written = 0;
-    if (offset > u->out_total) return fail(c, HPN_E_ARG, "offset %llu beyond the output's %llu bytes", (unsigned long long)offset, (unsigned long long)u->out_total);
-    const uint64_t n = u->out_total - offset < cap ? u->out_total - offset : cap;
-    if (n && !out) return fail(c, HPN_E_ARG, "out is NULL");
-    if (n) HPN_HIP(c, hipMemcpyAsync(out, (const uint8_t *)u->out.p + offset, n, hipMemcpyDefault, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    *written = n;
-    return HPN_OK;
+    const int rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_sort", written);
+    return rc != HPN_OK ? rc : session_write_slice(c, u->out, u->out_total, offset, out, cap, written);
 }
 
 }  // extern "C"

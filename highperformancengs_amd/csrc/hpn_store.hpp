@@ -1,8 +1,12 @@
-// hpn_store.hpp -- the device store behind hpn_fastq_uniq_* and hpn_fastq_sort_*: a stream's bytes are appended as they come and
-// framed WHERE THEY LIE (no carry is copied: the next chunk's framing starts at the first unfinished record), one descriptor per
-// record.  What a descriptor holds is the caller's: it hands in the kernel that writes them (kernels/fastq_uniq.hip: k_uniq_keys,
-// kernels/fastq_sort.hip: k_sort_frame) behind the line index of kernels/fastq_text.hip.
+// hpn_store.hpp -- the device store behind the six store-backed entry points (hpn_fastq_uniq_*, _uniqq_*, _usort_*, _sort_*, _pair_*,
+// hpn_twobit_pack_*) and the session around it.  The store: a stream's bytes are appended as they come and framed WHERE THEY
+// LIE (no carry is copied: the next chunk's framing starts at the first unfinished record), one descriptor per record.  What a
+// descriptor holds is the caller's: it hands in the kernel that writes them (kernels/fastq_uniq.hip: k_uniq_keys,
+// kernels/fastq_sort.hip: k_sort_frame) behind the line index of kernels/fastq_text.hip.  The session: one or two stores under
+// one byte limit, the _begin / _add / _finish / _write life cycle and its messages, and the info block the scans report through.
 #pragma once
+#include <string.h>
+
 #include "hpn_ctx.hpp"
 
 namespace hpn {
@@ -11,6 +15,20 @@ hipError_t launch_text_lines(const uint8_t *d_slot, uint32_t begin, uint32_t end
                              uint32_t nl_cap, u64 *d_status, uint32_t *d_state, hipStream_t st);
 uint64_t text_tiles1(uint32_t begin, uint32_t end);
 uint64_t text_tiles2(uint32_t nl_cap);
+// kernels/fastq_sort.hip: the framing behind kernels/sort_desc.hpp
+hipError_t launch_sort_frame(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
+                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st);
+// kernels/fastq_uniq.hip: the scans and the radix sort (radix_sort.hpp)
+hipError_t uniq_scan32(const uint32_t *d_in, uint32_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
+hipError_t uniq_scan64(const uint32_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
+hipError_t uniq_scan64w(const uint64_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
+uint64_t uniq_scan_tiles(uint64_t n);
+uint64_t uniq_sort_hist_words(uint32_t n);
+hipError_t uniq_sort_pairs(uint64_t *d_keys, uint32_t *d_vals, uint32_t n, int begin_bit, int end_bit, uint64_t *d_keys_tmp,
+                           uint32_t *d_vals_tmp, uint32_t *d_hist, uint32_t *d_offs, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err,
+                           hipStream_t st);
+hipError_t uniq_sort_pairs_digits(uint64_t *d_keys, uint32_t *d_vals, uint32_t n, uint32_t digits, uint64_t *d_keys_tmp, uint32_t *d_vals_tmp,
+                                  uint32_t *d_hist, uint32_t *d_offs, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t s);
 
 constexpr uint32_t kStorePad = 64;    // bytes in front of the stream's first byte and behind its last (the kernels' 16-byte loads)
 constexpr int kStateWords = 16;       // kernels/text_common.hpp: kTs*
@@ -128,6 +146,143 @@ inline int store_add(hpn_ctx *c, RecordStore &m, size_t desc_bytes, store_frame_
     *n_records = h[kTsRecs];
     m.n += h[kTsRecs];
     m.pos += h[kTsConsumed] - begin;
+    return HPN_OK;
+}
+
+// ---- the session ----  (`api`: the family's name in messages -- "hpn_fastq_sort", ... -- from the caller: there is no state before
+// the first _begin)
+
+// The device's info block (uint32 words): the scans' and sorts' hand-off ticket and error flag, then the family's own words.
+enum { kInfoTicket = 0, kInfoErr = 1, kInfoOwn = 2, kInfoWords = 16 };
+
+struct StoreSession {
+    int n_streams = 1;
+    RecordStore m[2];
+    uint64_t limit = 0;
+    bool open = false, finished = false;
+    uint32_t *d_info = nullptr, *h_info = nullptr;   // kInfoWords each; h_info: the pinned mirror
+    uint32_t *ticket() const { return d_info + kInfoTicket; }
+    uint32_t *err() const { return d_info + kInfoErr; }
+    const uint8_t *text(int k) const { return (const uint8_t *)m[k].store.p + kStorePad; }
+};
+
+inline int info_alloc(hpn_ctx *c, StoreSession &s)
+{
+    if (!s.d_info) {
+        HPN_HIP(c, hipMalloc((void **)&s.d_info, kInfoWords * sizeof(uint32_t)));
+        HPN_HIP(c, hipHostMalloc((void **)&s.h_info, kInfoWords * sizeof(uint32_t), hipHostMallocDefault));
+    }
+    return HPN_OK;
+}
+
+inline void info_free(StoreSession &s)
+{
+    if (s.d_info) (void)hipFree(s.d_info);
+    if (s.h_info) (void)hipHostFree(s.h_info);
+    s.d_info = s.h_info = nullptr;
+}
+
+// the info block on the host; waits for the stream
+inline int info_fetch(hpn_ctx *c, StoreSession &s)
+{
+    HPN_HIP(c, hipMemcpyAsync(s.h_info, s.d_info, kInfoWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HPN_HIP(c, hipStreamSynchronize(c->stream));
+    if (s.h_info[kInfoErr]) return fail(c, HPN_E_HIP, "prefix-scan hand-off timed out");
+    return HPN_OK;
+}
+
+inline void session_drop(StoreSession &s)
+{
+    for (RecordStore &m : s.m) store_release(m);
+    s.open = s.finished = false;
+}
+
+// _begin, behind the family's own drop: the info block on first use, the limit, open
+inline int session_begin(hpn_ctx *c, StoreSession &s, int n_streams, uint64_t max_bytes)
+{
+    const int rc = info_alloc(c, s);
+    if (rc != HPN_OK) return rc;
+    session_drop(s);
+    if (!max_bytes) {   // half of what is free: the other half is the reserve for the store's growth, the sorts' arrays and the output
+        size_t fr = 0, total = 0;
+        HPN_HIP(c, hipMemGetInfo(&fr, &total));
+        max_bytes = fr / 2;
+    }
+    s.n_streams = n_streams, s.limit = max_bytes;
+    s.open = true;
+    return HPN_OK;
+}
+
+// _add (Info: hpn_uniq_info / hpn_sort_info).  The limit counts every stream; info->store_bytes is every stream's bytes, or with
+// own_bytes the fed stream's.  A chunk beyond the limit and an irregular chunk close the session; NULL text and a span beyond
+// 2^31 - 4 KiB do not.
+template <class Info>
+int session_add(hpn_ctx *c, StoreSession *s, const char *api, int mate, size_t desc_bytes, store_frame_fn frame, const void *text,
+                uint64_t nbytes, int last, bool own_bytes, Info *info)
+{
+    if (!s || !s->open || s->finished) return fail(c, HPN_E_STATE, "%s_begin first (or the session was closed by an irregular chunk)", api);
+    if (mate < 0 || mate >= s->n_streams) return fail(c, HPN_E_ARG, "mate %d of a %s session", mate, s->n_streams > 1 ? "paired" : "single-end");
+    if (nbytes && !text) return fail(c, HPN_E_ARG, "text is NULL");
+    RecordStore &m = s->m[mate];
+    if (m.closed) return s->n_streams > 1 ? fail(c, HPN_E_STATE, "mate %d has had its last chunk", mate) : fail(c, HPN_E_STATE, "the stream has had its last chunk");
+    HPN_HIP(c, hipSetDevice(c->device));
+    memset(info, 0, sizeof *info);
+    const uint64_t span = m.len - m.pos + nbytes;
+    if (span >= (1ull << 31) - 4096) return fail(c, HPN_E_ARG, "chunk of %llu bytes (limit 2^31 - 4 KiB with the unfinished record)", (unsigned long long)nbytes);
+    const uint64_t stored = s->m[0].len + s->m[1].len + nbytes;
+    if (stored > s->limit) {
+        s->open = false;
+        return fail(c, HPN_E_CAPACITY, "the store needs %llu bytes, max_bytes is %llu", (unsigned long long)stored, (unsigned long long)s->limit);
+    }
+    bool close = false;
+    const int rc = store_add(c, m, desc_bytes, frame, text, nbytes, last, &info->n_records, &info->irregular, &close);
+    info->store_bytes = own_bytes ? m.len : s->m[0].len + s->m[1].len;
+    if (close) s->open = false;
+    return rc;
+}
+
+// What every _finish opens with: the session is open, every stream has had its last chunk; a stream without a byte gets its
+// (smallest) buffers, the info block is zeroed.
+inline int session_finish_begin(hpn_ctx *c, StoreSession *s, const char *api, size_t desc_bytes)
+{
+    if (!s || !s->open || s->finished) return fail(c, HPN_E_STATE, "no open %s session", api);
+    for (int k = 0; k < s->n_streams; ++k)
+        if (!s->m[k].closed) return fail(c, HPN_E_STATE, s->n_streams > 1 ? "every mate needs its last chunk first" : "the stream needs its last chunk first");
+    HPN_HIP(c, hipSetDevice(c->device));
+    int rc;
+    for (int k = 0; k < s->n_streams; ++k)
+        if ((rc = grow_keep(c, s->m[k].store, 2 * kStorePad, 0)) != HPN_OK || (rc = grow_keep(c, s->m[k].desc, desc_bytes, 0)) != HPN_OK) return rc;
+    HPN_HIP(c, hipMemsetAsync(s->d_info, 0, kInfoWords * sizeof(uint32_t), c->stream));
+    return HPN_OK;
+}
+
+// n 32-bit sizes -> n + 1 64-bit offsets; *total: the last one, on the host
+inline int scan_sizes(hpn_ctx *c, StoreSession &s, Scratch &status, const Scratch &size, const Scratch &off, uint64_t n, uint64_t *total)
+{
+    int rc;
+    if ((rc = need(c, status, uniq_scan_tiles(n) * 8)) != HPN_OK) return rc;
+    HPN_HIP(c, uniq_scan64((const uint32_t *)size.p, (uint64_t *)off.p, n, (u64 *)status.p, s.ticket(), s.err(), c->stream));
+    HPN_HIP(c, hipMemcpyAsync(total, (const uint64_t *)off.p + n, 8, hipMemcpyDeviceToHost, c->stream));
+    return info_fetch(c, s);
+}
+
+// What every _write opens with, and its slice copy: up to `cap` bytes of the `total` that lie in `out`, from `offset` on
+inline int session_write_begin(hpn_ctx *c, const StoreSession *s, const char *api, uint64_t *written)
+{
+    if (!s || !s->finished) return fail(c, HPN_E_STATE, "%s_finish first", api);
+    HPN_HIP(c, hipSetDevice(c->device));
+    *written = 0;
+    return HPN_OK;
+}
+
+inline int session_write_slice(hpn_ctx *c, const Scratch &out, uint64_t total, uint64_t offset, void *dst, uint64_t cap, uint64_t *written)
+{
+    if (offset > total) return fail(c, HPN_E_ARG, "offset %llu beyond the output's %llu bytes", (unsigned long long)offset, (unsigned long long)total);
+    const uint64_t n = total - offset < cap ? total - offset : cap;
+    if (n && !dst) return fail(c, HPN_E_ARG, "out is NULL");
+    if (n) HPN_HIP(c, hipMemcpyAsync(dst, (const uint8_t *)out.p + offset, n, hipMemcpyDefault, c->stream));
+    HPN_HIP(c, hipStreamSynchronize(c->stream));
+    *written = n;
     return HPN_OK;
 }
 

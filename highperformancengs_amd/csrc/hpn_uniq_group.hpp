@@ -1,5 +1,6 @@
-// hpn_uniq_group.hpp -- the grouping stage that hpn_fastq_uniq_* (hpn_uniq.hip) and hpn_fastq_uniqq_* (hpn_uniqq.hip) share: the
-// session's arrays, and uniq_group(): pair keys, the stable sort by grouping hash, flags, the host's ordering of clashing runs,
+// hpn_uniq_group.hpp -- the grouping stage that hpn_fastq_uniq_* (hpn_uniq.hip), hpn_fastq_uniqq_* (hpn_uniqq.hip) and
+// hpn_fastq_usort_* (hpn_usort.hip) share: the session (hpn_store.hpp) with the stage's arrays, uniq_match_mates() -- the name
+// check of a paired session -- and uniq_group(): pair keys, the stable sort by grouping hash, flags, the host's ordering of clashing runs,
 // group scan, reduce, the table-walk key and the sdscmp order.  Kernels: kernels/fastq_uniq.hip, kernels/radix_sort.hpp.
 //
 // dict.c's walk in closed form (derived from its rehashing: a table of 4 that doubles when full; a doubling walks the old
@@ -44,17 +45,10 @@ hipError_t launch_uniq_sizes(const void *d_desc, const uint32_t *d_list, const u
                              uint32_t *d_size, hipStream_t st);
 hipError_t launch_uniq_write(const uint8_t *d_text, const void *d_desc, const uint32_t *d_list, const uint32_t *d_rep,
                              const uint32_t *d_count, const uint64_t *d_off, uint32_t n_groups, uint8_t *d_out, int n_cu, hipStream_t st);
-hipError_t uniq_scan32(const uint32_t *d_in, uint32_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
-hipError_t uniq_scan64(const uint32_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
-hipError_t uniq_scan64w(const uint64_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
-uint64_t uniq_scan_tiles(uint64_t n);
-uint64_t uniq_sort_hist_words(uint32_t n);
-hipError_t uniq_sort_pairs(uint64_t *d_keys, uint32_t *d_vals, uint32_t n, int begin_bit, int end_bit, uint64_t *d_keys_tmp,
-                           uint32_t *d_vals_tmp, uint32_t *d_hist, uint32_t *d_offs, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err,
-                           hipStream_t st);
 
-// the device's info block (uint32 words)
-enum { kUiMaxLen = 0, kUiClash, kUiLastFirst, kUiBehind, kUiFirstBad, kUiTicket, kUiErr, kUiMaxCount, kUiWords = 16 };
+// The family's words of the session's info block.  The kernels of fastq_uniq.hip (words 0 .. 3) and fastq_usort.hip (7 .. 11)
+// number them from kUiBase on: they are handed uniq_kinfo().
+enum { kUiBase = kInfoOwn, kUiMaxLen = kUiBase, kUiClash, kUiLastFirst, kUiBehind, kUiFirstBad, kUiMaxCount };
 constexpr size_t kUniqDescBytes = 32;     // kernels/uniq_desc.hpp: UniqDesc
 
 struct UniqDescHost {   // UniqDesc as the host reads it (runs of equal hashes over different bytes)
@@ -66,14 +60,11 @@ static_assert(sizeof(UniqDescHost) == kUniqDescBytes, "UniqDesc layout");
 }  // namespace hpn
 
 struct hpn_uniq_state {
-    int paired = 0;
-    uint64_t limit = 0;
+    hpn::StoreSession s;
+    int paired = 0;   // s.n_streams - 1
     uint32_t hash_bits = 0;
-    bool open = false, finished = false;
-    hpn::RecordStore m[2];
     hpn::Scratch hash, order, djb, sumq, flag, gid, count, best, first, rep, mark, rank, key, val, key_tmp, val_tmp, hist, offs, status,
         list_table, list_key, size, off, out;
-    uint32_t *d_info = nullptr, *h_info = nullptr;
     uint32_t N = 0, U = 0;
     uint64_t out_total = 0;
     int cached_which = -1, cached_mate = -1;
@@ -81,41 +72,24 @@ struct hpn_uniq_state {
 
 namespace hpn {
 
+inline uint32_t *uniq_kinfo(hpn_uniq_state *u) { return u->s.d_info + kUiBase; }
+
 inline void uniq_drop_session(hpn_uniq_state *u)
 {
-    for (RecordStore &m : u->m) {
-        store_release(m);
-    }
+    session_drop(u->s);
     Scratch *ss[] = {&u->hash, &u->order, &u->djb, &u->sumq, &u->flag, &u->gid, &u->count, &u->best, &u->first, &u->rep, &u->mark, &u->rank,
                      &u->key, &u->val, &u->key_tmp, &u->val_tmp, &u->hist, &u->offs, &u->status, &u->list_table, &u->list_key, &u->size,
                      &u->off, &u->out};
     for (Scratch *s : ss) release_scratch(*s);
-    u->open = u->finished = false;
     u->cached_which = u->cached_mate = -1;
 }
 
-inline int uniq_info_alloc(hpn_ctx *c, hpn_uniq_state *u)
+// _begin of the three families that group: the session's, and the grouping hash's width
+inline int uniq_begin(hpn_ctx *c, hpn_uniq_state *u, int paired, uint64_t max_bytes, uint32_t hash_bits)
 {
-    if (!u->d_info) {
-        HPN_HIP(c, hipMalloc((void **)&u->d_info, kUiWords * sizeof(uint32_t)));
-        HPN_HIP(c, hipHostMalloc((void **)&u->h_info, kUiWords * sizeof(uint32_t), hipHostMallocDefault));
-    }
-    return HPN_OK;
-}
-
-inline void uniq_info_free(hpn_uniq_state *u)
-{
-    if (u->d_info) (void)hipFree(u->d_info);
-    if (u->h_info) (void)hipHostFree(u->h_info);
-    u->d_info = u->h_info = nullptr;
-}
-
-inline int uniq_fetch_info(hpn_ctx *c, hpn_uniq_state *u)
-{
-    HPN_HIP(c, hipMemcpyAsync(u->h_info, u->d_info, kUiWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (u->h_info[kUiErr]) return fail(c, HPN_E_HIP, "prefix-scan hand-off timed out");
-    return HPN_OK;
+    const int rc = session_begin(c, u->s, paired ? 2 : 1, max_bytes);
+    u->paired = paired ? 1 : 0, u->hash_bits = hash_bits;
+    return rc;
 }
 
 inline int uniq_sort(hpn_ctx *c, hpn_uniq_state *u, uint64_t *keys, uint32_t *vals, uint32_t n, int begin_bit, int end_bit)
@@ -127,7 +101,7 @@ inline int uniq_sort(hpn_ctx *c, hpn_uniq_state *u, uint64_t *keys, uint32_t *va
         (rc = need(c, u->status, uniq_scan_tiles(hw > n ? hw : n) * 8)) != HPN_OK)
         return rc;
     HPN_HIP(c, uniq_sort_pairs(keys, vals, n, begin_bit, end_bit, (uint64_t *)u->key_tmp.p, (uint32_t *)u->val_tmp.p, (uint32_t *)u->hist.p,
-                               (uint32_t *)u->offs.p, (u64 *)u->status.p, u->d_info + kUiTicket, u->d_info + kUiErr, c->stream));
+                               (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.ticket(), u->s.err(), c->stream));
     return HPN_OK;
 }
 
@@ -139,10 +113,10 @@ inline int uniq_order_clashing_runs(hpn_ctx *c, hpn_uniq_state *u)
     std::vector<uint8_t> text[2];
     std::vector<UniqDescHost> desc[2];
     for (int k = 0; k <= u->paired; ++k) {
-        text[k].resize(u->m[k].len + 1);
+        text[k].resize(u->s.m[k].len + 1);
         desc[k].resize(N ? N : 1);
-        if (u->m[k].len) HPN_HIP(c, hipMemcpy(text[k].data(), (const uint8_t *)u->m[k].store.p + kStorePad, u->m[k].len, hipMemcpyDeviceToHost));
-        HPN_HIP(c, hipMemcpy(desc[k].data(), u->m[k].desc.p, (size_t)N * kUniqDescBytes, hipMemcpyDeviceToHost));
+        if (u->s.m[k].len) HPN_HIP(c, hipMemcpy(text[k].data(), (const uint8_t *)u->s.m[k].store.p + kStorePad, u->s.m[k].len, hipMemcpyDeviceToHost));
+        HPN_HIP(c, hipMemcpy(desc[k].data(), u->s.m[k].desc.p, (size_t)N * kUniqDescBytes, hipMemcpyDeviceToHost));
     }
     std::vector<uint64_t> hash(N);
     std::vector<uint32_t> order(N);
@@ -172,7 +146,31 @@ inline int uniq_order_clashing_runs(hpn_ctx *c, hpn_uniq_state *u)
     return HPN_OK;
 }
 
-// The grouping stage over the u->N records (pairs) of the session, u->d_info zeroed by the caller.  Leaves: order[] -- the record
+// The mates' names of a paired session, ordinal by ordinal (launch_uniq_names): *N -- mate 0's records on entry -- becomes the
+// pairs that count, *unmatched the first ordinal whose mate is named otherwise or missing (the caller's -1 stays: none) and
+// unmatched_name mate 0's name there.  A single-end session is left as it is.
+inline int uniq_match_mates(hpn_ctx *c, hpn_uniq_state *u, uint32_t *N, int64_t *unmatched, char *unmatched_name)
+{
+    if (!u->paired) return HPN_OK;
+    int rc;
+    const uint8_t *t0 = u->s.text(0);
+    const void *d0 = u->s.m[0].desc.p;
+    const uint32_t n2 = (uint32_t)u->s.m[1].n, both = *N < n2 ? *N : n2;
+    HPN_HIP(c, hipMemsetAsync(u->s.d_info + kUiFirstBad, 0xff, sizeof(uint32_t), c->stream));
+    HPN_HIP(c, launch_uniq_names(t0, d0, u->s.text(1), u->s.m[1].desc.p, both, u->s.d_info + kUiFirstBad, c->stream));
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if (u->s.h_info[kUiFirstBad] != 0xffffffffu) *N = u->s.h_info[kUiFirstBad], *unmatched = *N;
+    else if (*N > n2) *N = n2, *unmatched = n2;   // the mate is missing
+    if (*unmatched >= 0) {
+        UniqDescHost d;
+        HPN_HIP(c, hipMemcpy(&d, (const uint8_t *)d0 + (size_t)*N * kUniqDescBytes, kUniqDescBytes, hipMemcpyDeviceToHost));
+        HPN_HIP(c, hipMemcpy(unmatched_name, t0 + d.off, d.nlen, hipMemcpyDeviceToHost));
+        unmatched_name[d.nlen] = 0;
+    }
+    return HPN_OK;
+}
+
+// The grouping stage over the u->N records (pairs) of the session, the info block zeroed by the caller.  Leaves: order[] -- the record
 // ordinals sorted stably by grouping hash (clashing runs by their bytes), so a group's members are adjacent and ascending; flag[]
 // (1 where a group opens), gid[] (its exclusive scan), and per group count, first, rep; u->U; list_table[] and, single-end,
 // list_key[]: the groups in the order of the table walk and in sdscmp order.
@@ -181,8 +179,8 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
     int rc;
     const int paired = u->paired;
     const uint32_t N = u->N;
-    const uint8_t *t0 = (const uint8_t *)u->m[0].store.p + kStorePad, *t1 = paired ? (const uint8_t *)u->m[1].store.p + kStorePad : nullptr;
-    const void *d0 = u->m[0].desc.p, *d1 = paired ? u->m[1].desc.p : nullptr;
+    const uint8_t *t0 = (const uint8_t *)u->s.m[0].store.p + kStorePad, *t1 = paired ? (const uint8_t *)u->s.m[1].store.p + kStorePad : nullptr;
+    const void *d0 = u->s.m[0].desc.p, *d1 = paired ? u->s.m[1].desc.p : nullptr;
     if ((rc = need(c, u->hash, (size_t)N * 8)) != HPN_OK || (rc = need(c, u->order, (size_t)N * 4)) != HPN_OK ||
         (rc = need(c, u->djb, (size_t)N * 4)) != HPN_OK || (rc = need(c, u->sumq, (size_t)N * 4)) != HPN_OK ||
         (rc = need(c, u->flag, (size_t)N * 4)) != HPN_OK || (rc = need(c, u->gid, ((size_t)N + 1) * 4)) != HPN_OK ||
@@ -192,24 +190,24 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
     uint64_t *hash = (uint64_t *)u->hash.p;
     uint32_t *order = (uint32_t *)u->order.p, *djb = (uint32_t *)u->djb.p, *sumq = (uint32_t *)u->sumq.p, *flag = (uint32_t *)u->flag.p;
     uint32_t *gid = (uint32_t *)u->gid.p, *mark = (uint32_t *)u->mark.p, *rank = (uint32_t *)u->rank.p;
-    uint32_t *ticket = u->d_info + kUiTicket, *err = u->d_info + kUiErr;
+    uint32_t *ticket = u->s.ticket(), *err = u->s.err();
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTally], c->stream));
     const uint64_t mask = u->hash_bits ? (1ull << u->hash_bits) - 1 : ~0ull;
-    HPN_HIP(c, launch_uniq_pair(t0, d0, t1, d1, paired, N, mask, hash, order, djb, sumq, u->d_info, c->stream));
+    HPN_HIP(c, launch_uniq_pair(t0, d0, t1, d1, paired, N, mask, hash, order, djb, sumq, uniq_kinfo(u), c->stream));
     if ((rc = uniq_sort(c, u, hash, order, N, 0, u->hash_bits ? (int)u->hash_bits : 64)) != HPN_OK) return rc;
-    HPN_HIP(c, launch_uniq_flags(t0, d0, t1, d1, paired, hash, order, N, flag, u->d_info, c->stream));
-    if ((rc = uniq_fetch_info(c, u)) != HPN_OK) return rc;
-    *hash_clashes = u->h_info[kUiClash];
-    const uint32_t max_len = u->h_info[kUiMaxLen];
-    if (u->h_info[kUiClash]) {
+    HPN_HIP(c, launch_uniq_flags(t0, d0, t1, d1, paired, hash, order, N, flag, uniq_kinfo(u), c->stream));
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    *hash_clashes = u->s.h_info[kUiClash];
+    const uint32_t max_len = u->s.h_info[kUiMaxLen];
+    if (u->s.h_info[kUiClash]) {
         if ((rc = uniq_order_clashing_runs(c, u)) != HPN_OK) return rc;
-        HPN_HIP(c, launch_uniq_flags(t0, d0, t1, d1, paired, hash, order, N, flag, u->d_info, c->stream));
+        HPN_HIP(c, launch_uniq_flags(t0, d0, t1, d1, paired, hash, order, N, flag, uniq_kinfo(u), c->stream));
     }
     if ((rc = need(c, u->status, uniq_scan_tiles(N) * 8)) != HPN_OK) return rc;
     HPN_HIP(c, uniq_scan32(flag, gid, N, (u64 *)u->status.p, ticket, err, c->stream));
     uint32_t U = 0;
     HPN_HIP(c, hipMemcpyAsync(&U, gid + N, 4, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = uniq_fetch_info(c, u)) != HPN_OK) return rc;
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
     u->U = U;
     if ((rc = need(c, u->count, (size_t)U * 4)) != HPN_OK || (rc = need(c, u->best, (size_t)U * 8)) != HPN_OK ||
         (rc = need(c, u->first, (size_t)U * 4)) != HPN_OK || (rc = need(c, u->rep, (size_t)U * 4)) != HPN_OK ||
@@ -220,10 +218,10 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
     uint64_t *key = (uint64_t *)u->key.p;
     uint32_t *val = (uint32_t *)u->val.p;
     HPN_HIP(c, launch_uniq_reduce(order, flag, gid, sumq, N, U, (uint32_t *)u->count.p, (uint64_t *)u->best.p, first, (uint32_t *)u->rep.p,
-                                  u->d_info, c->stream));
+                                  uniq_kinfo(u), c->stream));
     HPN_HIP(c, launch_uniq_mark(first, U, mark, N, c->stream));
     HPN_HIP(c, uniq_scan32(mark, rank, N, (u64 *)u->status.p, ticket, err, c->stream));
-    if ((rc = uniq_fetch_info(c, u)) != HPN_OK) return rc;
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
     // the table's size and the parity of its doublings
     auto epoch = [](uint32_t j) { return j < 4 ? 0u : (uint32_t)(31 - __builtin_clz(j)) - 1u; };
     uint64_t S = 0;
@@ -232,7 +230,7 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
         S = 4;
         while (S < U) S *= 2;
         K = epoch(U - 1);
-        if (replace_doubles && U >= 4 && (U & (U - 1)) == 0 && u->h_info[kUiBehind]) S *= 2, K += 1;
+        if (replace_doubles && U >= 4 && (U & (U - 1)) == 0 && u->s.h_info[kUiBehind]) S *= 2, K += 1;
     }
     *hash_size = S;
     int slot_bits = 0;
@@ -250,7 +248,7 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
     }
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTally], c->stream));
     c->ev_valid[kFamTally] = true;
-    return uniq_fetch_info(c, u);
+    return info_fetch(c, u->s);
 }
 
 }  // namespace hpn

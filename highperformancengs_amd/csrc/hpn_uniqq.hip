@@ -58,7 +58,7 @@ int count_list(hpn_ctx *c, hpn_uniqq_state *q)
     HPN_HIP(c, launch_uniqq_count_key((const uint32_t *)u->list_table.p, (const uint32_t *)u->count.p, U, key, val, c->stream));
     if ((rc = uniq_sort(c, u, key, val, U, 32, 32 + count_bits)) != HPN_OK) return rc;
     HPN_HIP(c, hipMemcpyAsync(q->list_count.p, val, (size_t)U * 4, hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = uniq_fetch_info(c, u)) != HPN_OK) return rc;
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
     q->have_count_list = true;
     return HPN_OK;
 }
@@ -76,12 +76,12 @@ int place_groups(hpn_ctx *c, hpn_uniqq_state *q, int which, uint64_t *total)
         return rc;
     const uint32_t *order = (const uint32_t *)u->order.p, *start = (const uint32_t *)q->start.p, *count = (const uint32_t *)u->count.p;
     const uint64_t *P = (const uint64_t *)q->P.p;
-    HPN_HIP(c, launch_uniqq_sizes(u->m[0].desc.p, order, list, start, count, P, U, (uint64_t *)q->total.p, c->stream));
-    HPN_HIP(c, uniq_scan64w((const uint64_t *)q->total.p, (uint64_t *)q->goff.p, U, (u64 *)u->status.p, u->d_info + kUiTicket, u->d_info + kUiErr,
+    HPN_HIP(c, launch_uniqq_sizes(u->s.m[0].desc.p, order, list, start, count, P, U, (uint64_t *)q->total.p, c->stream));
+    HPN_HIP(c, uniq_scan64w((const uint64_t *)q->total.p, (uint64_t *)q->goff.p, U, (u64 *)u->status.p, u->s.ticket(), u->s.err(),
                             c->stream));
-    HPN_HIP(c, launch_uniqq_base(u->m[0].desc.p, order, list, start, count, P, (const uint64_t *)q->goff.p, U, (uint64_t *)q->base.p, c->stream));
+    HPN_HIP(c, launch_uniqq_base(u->s.m[0].desc.p, order, list, start, count, P, (const uint64_t *)q->goff.p, U, (uint64_t *)q->base.p, c->stream));
     HPN_HIP(c, hipMemcpyAsync(total, (const uint64_t *)q->goff.p + U, 8, hipMemcpyDeviceToHost, c->stream));
-    return uniq_fetch_info(c, u);
+    return info_fetch(c, u->s);
 }
 
 // the whole text of one output on the device (u->out, u->out_total bytes)
@@ -94,7 +94,7 @@ int build_output(hpn_ctx *c, hpn_uniqq_state *q, int which)
     if ((rc = place_groups(c, q, which, &total)) != HPN_OK) return rc;
     if ((rc = need(c, u->out, total)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
-    HPN_HIP(c, launch_uniqq_write((const uint8_t *)u->m[0].store.p + kStorePad, u->m[0].desc.p, (const uint32_t *)u->order.p,
+    HPN_HIP(c, launch_uniqq_write((const uint8_t *)u->s.m[0].store.p + kStorePad, u->s.m[0].desc.p, (const uint32_t *)u->order.p,
                                   (const uint32_t *)u->flag.p, (const uint32_t *)u->gid.p, (const uint32_t *)u->count.p, (const uint64_t *)q->P.p,
                                   (const uint64_t *)q->base.p, u->N, (uint8_t *)u->out.p, c->n_cu, c->stream));
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
@@ -111,7 +111,7 @@ void uniqq_release(hpn_ctx *c)
 {
     if (!c->qq) return;
     drop_session(c->qq);
-    uniq_info_free(&c->qq->g);
+    info_free(c->qq->g.s);
     delete c->qq;
     c->qq = nullptr;
 }
@@ -125,41 +125,14 @@ int hpn_fastq_uniqq_begin(hpn_ctx *c, uint64_t max_bytes, uint32_t hash_bits)
     if (hash_bits > 63) return fail(c, HPN_E_ARG, "hash_bits %u (0 = all 64, or 1 .. 63)", hash_bits);
     HPN_HIP(c, hipSetDevice(c->device));
     if (!c->qq) c->qq = new hpn_uniqq_state;
-    hpn_uniqq_state *q = c->qq;
-    int rc = uniq_info_alloc(c, &q->g);
-    if (rc != HPN_OK) return rc;
-    drop_session(q);
-    if (!max_bytes) {   // half of what is free: the other half is the reserve for the store's growth, the sorts' arrays and the output
-        size_t fr = 0, total = 0;
-        HPN_HIP(c, hipMemGetInfo(&fr, &total));
-        max_bytes = fr / 2;
-    }
-    q->g.paired = 0, q->g.limit = max_bytes, q->g.hash_bits = hash_bits;
-    q->g.open = true;
-    return HPN_OK;
+    drop_session(c->qq);
+    return uniq_begin(c, &c->qq->g, 0, max_bytes, hash_bits);
 }
 
 int hpn_fastq_uniqq_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_uniq_state *u = c->qq ? &c->qq->g : nullptr;
-    if (!u || !u->open || u->finished) return fail(c, HPN_E_STATE, "hpn_fastq_uniqq_begin first (or the session was closed by an irregular chunk)");
-    if (nbytes && !text) return fail(c, HPN_E_ARG, "text is NULL");
-    RecordStore &m = u->m[0];
-    if (m.closed) return fail(c, HPN_E_STATE, "the stream has had its last chunk");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    const uint64_t span = m.len - m.pos + nbytes;
-    if (span >= (1ull << 31) - 4096) return fail(c, HPN_E_ARG, "chunk of %llu bytes (limit 2^31 - 4 KiB with the unfinished record)", (unsigned long long)nbytes);
-    if (m.len + nbytes > u->limit) {
-        u->open = false;
-        return fail(c, HPN_E_CAPACITY, "the store needs %llu bytes, max_bytes is %llu", (unsigned long long)(m.len + nbytes), (unsigned long long)u->limit);
-    }
-    bool close = false;
-    const int rc = store_add(c, m, kUniqDescBytes, launch_uniqq_keys, text, nbytes, last, &info->n_records, &info->irregular, &close);
-    info->store_bytes = m.len;
-    if (close) u->open = false;
-    return rc;
+    return session_add(c, c->qq ? &c->qq->g.s : nullptr, "hpn_fastq_uniqq", 0, kUniqDescBytes, launch_uniqq_keys, text, nbytes, last, false, info);
 }
 
 int hpn_fastq_uniqq_finish(hpn_ctx *c, hpn_uniqq_result *res)
@@ -167,14 +140,10 @@ int hpn_fastq_uniqq_finish(hpn_ctx *c, hpn_uniqq_result *res)
     if (!c || !res) return HPN_E_ARG;
     hpn_uniqq_state *q = c->qq;
     hpn_uniq_state *u = q ? &q->g : nullptr;
-    if (!u || !u->open || u->finished) return fail(c, HPN_E_STATE, "no open hpn_fastq_uniqq session");
-    if (!u->m[0].closed) return fail(c, HPN_E_STATE, "the stream needs its last chunk first");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(res, 0, sizeof *res);
     int rc;
-    if ((rc = grow_keep(c, u->m[0].store, 2 * kStorePad, 0)) != HPN_OK || (rc = grow_keep(c, u->m[0].desc, kUniqDescBytes, 0)) != HPN_OK) return rc;   // (a stream without a byte has no buffers yet)
-    HPN_HIP(c, hipMemsetAsync(u->d_info, 0, kUiWords * sizeof(uint32_t), c->stream));
-    const uint32_t N = u->N = (uint32_t)u->m[0].n;
+    if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_uniqq", kUniqDescBytes)) != HPN_OK) return rc;
+    memset(res, 0, sizeof *res);
+    const uint32_t N = u->N = (uint32_t)u->s.m[0].n;
     res->n_records = N;
     if ((rc = uniq_group(c, u, false, &res->hash_size, &res->hash_clashes)) != HPN_OK) return rc;
     const uint32_t U = u->U;
@@ -183,13 +152,13 @@ int hpn_fastq_uniqq_finish(hpn_ctx *c, hpn_uniqq_result *res)
     if ((rc = need(c, q->len, (size_t)N * 4)) != HPN_OK || (rc = need(c, q->P, ((size_t)N + 1) * 8)) != HPN_OK ||
         (rc = need(c, q->start, (size_t)U * 4)) != HPN_OK || (rc = need(c, u->status, uniq_scan_tiles(N) * 8)) != HPN_OK)
         return rc;
-    HPN_HIP(c, launch_uniqq_len(u->m[0].desc.p, (const uint32_t *)u->order.p, (const uint32_t *)u->flag.p, (const uint32_t *)u->gid.p,
-                                (const uint32_t *)u->count.p, N, (uint32_t *)q->len.p, (uint32_t *)q->start.p, u->d_info + kUiMaxCount, c->stream));
-    HPN_HIP(c, uniq_scan64((const uint32_t *)q->len.p, (uint64_t *)q->P.p, N, (u64 *)u->status.p, u->d_info + kUiTicket, u->d_info + kUiErr, c->stream));
-    if ((rc = uniq_fetch_info(c, u)) != HPN_OK) return rc;
-    res->max_count = q->max_count = u->h_info[kUiMaxCount];
+    HPN_HIP(c, launch_uniqq_len(u->s.m[0].desc.p, (const uint32_t *)u->order.p, (const uint32_t *)u->flag.p, (const uint32_t *)u->gid.p,
+                                (const uint32_t *)u->count.p, N, (uint32_t *)q->len.p, (uint32_t *)q->start.p, u->s.d_info + kUiMaxCount, c->stream));
+    HPN_HIP(c, uniq_scan64((const uint32_t *)q->len.p, (uint64_t *)q->P.p, N, (u64 *)u->status.p, u->s.ticket(), u->s.err(), c->stream));
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    res->max_count = q->max_count = u->s.h_info[kUiMaxCount];
     if ((rc = place_groups(c, q, HPN_UNIQQ_KEY_ORDER, &res->out_bytes)) != HPN_OK) return rc;   // (both orders hold the same groups)
-    u->finished = true;
+    u->s.finished = true;
     return HPN_OK;
 }
 
@@ -198,19 +167,11 @@ int hpn_fastq_uniqq_write(hpn_ctx *c, int which, uint64_t offset, void *out, uin
     if (!c || !written) return HPN_E_ARG;
     hpn_uniqq_state *q = c->qq;
     hpn_uniq_state *u = q ? &q->g : nullptr;
-    if (!u || !u->finished) return fail(c, HPN_E_STATE, "hpn_fastq_uniqq_finish first");
-    if (which != HPN_UNIQQ_KEY_ORDER && which != HPN_UNIQQ_COUNT_ORDER) return fail(c, HPN_E_ARG, "unknown output %d", which);
-    HPN_HIP(c, hipSetDevice(c->device));
-    *written = 0;
     int rc;
+    if ((rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_uniqq", written)) != HPN_OK) return rc;
+    if (which != HPN_UNIQQ_KEY_ORDER && which != HPN_UNIQQ_COUNT_ORDER) return fail(c, HPN_E_ARG, "unknown output %d", which);
     if (u->cached_which != which && (rc = build_output(c, q, which)) != HPN_OK) return rc;
-    if (offset > u->out_total) return fail(c, HPN_E_ARG, "offset %llu beyond the output's %llu bytes", (unsigned long long)offset, (unsigned long long)u->out_total);
-    const uint64_t n = u->out_total - offset < cap ? u->out_total - offset : cap;
-    if (n && !out) return fail(c, HPN_E_ARG, "out is NULL");
-    if (n) HPN_HIP(c, hipMemcpyAsync(out, (const uint8_t *)u->out.p + offset, n, hipMemcpyDefault, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    *written = n;
-    return HPN_OK;
+    return session_write_slice(c, u->out, u->out_total, offset, out, cap, written);
 }
 
 }  // extern "C"

@@ -55,15 +55,15 @@ int build_output(hpn_ctx *c, hpn_usort_state *q, int mate)
     if ((rc = need(c, q->size64, (size_t)U * 8)) != HPN_OK || (rc = need(c, u->off, ((size_t)U + 1) * 8)) != HPN_OK ||
         (rc = need(c, u->status, uniq_scan_tiles(U) * 8)) != HPN_OK)
         return rc;
-    const uint8_t *t0 = (const uint8_t *)u->m[0].store.p + kStorePad, *t1 = paired ? (const uint8_t *)u->m[1].store.p + kStorePad : nullptr;
-    const void *d0 = u->m[0].desc.p, *d1 = paired ? u->m[1].desc.p : nullptr;
+    const uint8_t *t0 = (const uint8_t *)u->s.m[0].store.p + kStorePad, *t1 = paired ? (const uint8_t *)u->s.m[1].store.p + kStorePad : nullptr;
+    const void *d0 = u->s.m[0].desc.p, *d1 = paired ? u->s.m[1].desc.p : nullptr;
     const uint32_t *list = (const uint32_t *)q->list.p, *first = (const uint32_t *)u->first.p, *count = (const uint32_t *)u->count.p;
     HPN_HIP(c, launch_usort_sizes(t0, d0, t1, d1, paired, mate, list, first, count, U, q->seq_len, (uint64_t *)q->size64.p, c->stream));
-    HPN_HIP(c, uniq_scan64w((const uint64_t *)q->size64.p, (uint64_t *)u->off.p, U, (u64 *)u->status.p, u->d_info + kUiTicket, u->d_info + kUiErr,
+    HPN_HIP(c, uniq_scan64w((const uint64_t *)q->size64.p, (uint64_t *)u->off.p, U, (u64 *)u->status.p, u->s.ticket(), u->s.err(),
                             c->stream));
     uint64_t total = 0;
     HPN_HIP(c, hipMemcpyAsync(&total, (const uint64_t *)u->off.p + U, 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = uniq_fetch_info(c, u)) != HPN_OK) return rc;
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
     u->cached_mate = -1;
     if ((rc = need(c, u->out, total)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
@@ -90,7 +90,7 @@ void usort_release(hpn_ctx *c)
 {
     if (!c->us) return;
     drop_session(c->us);
-    uniq_info_free(&c->us->g);
+    info_free(c->us->g.s);
     delete c->us;
     c->us = nullptr;
 }
@@ -104,46 +104,19 @@ int hpn_fastq_usort_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t h
     if (hash_bits > 63) return fail(c, HPN_E_ARG, "hash_bits %u (0 = all 64, or 1 .. 63)", hash_bits);
     HPN_HIP(c, hipSetDevice(c->device));
     if (!c->us) c->us = new hpn_usort_state;
-    hpn_usort_state *q = c->us;
-    int rc = uniq_info_alloc(c, &q->g);
-    if (rc != HPN_OK) return rc;
-    drop_session(q);
-    if (!max_bytes) {   // half of what is free: the other half is the reserve for the store's growth, the sorts' arrays and the output
-        size_t fr = 0, total = 0;
-        HPN_HIP(c, hipMemGetInfo(&fr, &total));
-        max_bytes = fr / 2;
-    }
-    q->g.paired = paired ? 1 : 0, q->g.limit = max_bytes, q->g.hash_bits = hash_bits;
-    q->g.open = true;
-    return HPN_OK;
+    drop_session(c->us);
+    return uniq_begin(c, &c->us->g, paired, max_bytes, hash_bits);
 }
 
 int hpn_fastq_usort_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
     hpn_usort_state *q = c->us;
-    hpn_uniq_state *u = q ? &q->g : nullptr;
-    if (!u || !u->open || u->finished) return fail(c, HPN_E_STATE, "hpn_fastq_usort_begin first (or the session was closed by an irregular chunk)");
-    if (mate < 0 || mate > u->paired) return fail(c, HPN_E_ARG, "mate %d of a %s session", mate, u->paired ? "paired" : "single-end");
-    if (nbytes && !text) return fail(c, HPN_E_ARG, "text is NULL");
-    RecordStore &m = u->m[mate];
-    if (m.closed) return fail(c, HPN_E_STATE, "mate %d has had its last chunk", mate);
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    const uint64_t span = m.len - m.pos + nbytes;
-    if (span >= (1ull << 31) - 4096) return fail(c, HPN_E_ARG, "chunk of %llu bytes (limit 2^31 - 4 KiB with the unfinished record)", (unsigned long long)nbytes);
-    const uint64_t stored = u->m[0].len + u->m[1].len + nbytes;
-    if (stored > u->limit) {
-        u->open = false;
-        return fail(c, HPN_E_CAPACITY, "the store needs %llu bytes, max_bytes is %llu", (unsigned long long)stored, (unsigned long long)u->limit);
-    }
-    bool close = false;
-    const int rc = store_add(c, m, kUniqDescBytes, launch_uniqq_keys, text, nbytes, last, &info->n_records, &info->irregular, &close);
-    info->store_bytes = u->m[0].len + u->m[1].len;
-    if (close) u->open = false;
+    const uint64_t span = q && mate == 0 ? q->g.s.m[0].len - q->g.s.m[0].pos + nbytes : 0;   // (what the call frames, when it gets that far)
+    const int rc = session_add(c, q ? &q->g.s : nullptr, "hpn_fastq_usort", mate, kUniqDescBytes, launch_uniqq_keys, text, nbytes, last, false, info);
     // the line index of the stream's last stretch tells whether one open line follows the last record (k_uniq_keys takes it as
     // no record; count_read's gzgets returns it)
-    if (rc == HPN_OK && !close && last && mate == 0 && span)
+    if (rc == HPN_OK && q->g.s.open && last && mate == 0 && span)
         q->lone_line = (c->h_tstate[kTsLines] & 3u) == 1u && c->h_tstate[kTsUnterminated] ? 1 : 0;
     return rc;
 }
@@ -153,41 +126,23 @@ int hpn_fastq_usort_finish(hpn_ctx *c, hpn_usort_result *res)
     if (!c || !res) return HPN_E_ARG;
     hpn_usort_state *q = c->us;
     hpn_uniq_state *u = q ? &q->g : nullptr;
-    if (!u || !u->open || u->finished) return fail(c, HPN_E_STATE, "no open hpn_fastq_usort session");
-    if (!u->m[0].closed || (u->paired && !u->m[1].closed)) return fail(c, HPN_E_STATE, "every mate needs its last chunk first");
-    HPN_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_usort", kUniqDescBytes)) != HPN_OK) return rc;
     memset(res, 0, sizeof *res);
     res->unmatched = -1;
-    int rc;
     const int paired = u->paired;
-    for (int k = 0; k <= paired; ++k)   // (a mate without a byte has no buffers yet)
-        if ((rc = grow_keep(c, u->m[k].store, 2 * kStorePad, 0)) != HPN_OK || (rc = grow_keep(c, u->m[k].desc, kUniqDescBytes, 0)) != HPN_OK) return rc;
-    const uint8_t *t0 = (const uint8_t *)u->m[0].store.p + kStorePad, *t1 = paired ? (const uint8_t *)u->m[1].store.p + kStorePad : nullptr;
-    const void *d0 = u->m[0].desc.p, *d1 = paired ? u->m[1].desc.p : nullptr;
-    HPN_HIP(c, hipMemsetAsync(u->d_info, 0, kUiWords * sizeof(uint32_t), c->stream));
-    HPN_HIP(c, hipMemsetAsync(u->d_info + kUsFirstSeq, 0xff, sizeof(uint32_t), c->stream));
-    const uint64_t e = u->m[0].n + q->lone_line;
+    const uint8_t *t0 = u->s.text(0), *t1 = paired ? u->s.text(1) : nullptr;
+    const void *d0 = u->s.m[0].desc.p, *d1 = paired ? u->s.m[1].desc.p : nullptr;
+    HPN_HIP(c, hipMemsetAsync(uniq_kinfo(u) + kUsFirstSeq, 0xff, sizeof(uint32_t), c->stream));
+    const uint64_t e = u->s.m[0].n + q->lone_line;
     const uint64_t S = (uint64_t)(1.34 * (double)e);   // HSIZE tblsiz=1.34*elecnt (:117)
     res->table_reads = e, res->hash_size = S;
-    uint32_t N = (uint32_t)u->m[0].n;
-    if (paired) {   // the rule of hpn_fastq_uniq_finish
-        const uint32_t n2 = (uint32_t)u->m[1].n, both = N < n2 ? N : n2;
-        HPN_HIP(c, hipMemsetAsync(u->d_info + kUiFirstBad, 0xff, sizeof(uint32_t), c->stream));
-        HPN_HIP(c, launch_uniq_names(t0, d0, t1, d1, both, u->d_info + kUiFirstBad, c->stream));
-        if ((rc = uniq_fetch_info(c, u)) != HPN_OK) return rc;
-        if (u->h_info[kUiFirstBad] != 0xffffffffu) N = u->h_info[kUiFirstBad], res->unmatched = N;
-        else if (N > n2) N = n2, res->unmatched = n2;   // the mate is missing
-        if (res->unmatched >= 0) {
-            UniqDescHost d;
-            HPN_HIP(c, hipMemcpy(&d, (const uint8_t *)d0 + (size_t)N * kUniqDescBytes, kUniqDescBytes, hipMemcpyDeviceToHost));
-            HPN_HIP(c, hipMemcpy(res->unmatched_name, t0 + d.off, d.nlen, hipMemcpyDeviceToHost));
-            res->unmatched_name[d.nlen] = 0;
-        }
-    }
+    uint32_t N = (uint32_t)u->s.m[0].n;
+    if ((rc = uniq_match_mates(c, u, &N, &res->unmatched, res->unmatched_name)) != HPN_OK) return rc;
     u->N = N;
     res->n_records = N;
     if (N && e < 10) {   // total_reads_count % (elecnt / 10) behind the first record (:161)
-        u->open = false;
+        u->s.open = false;
         res->no_answer = HPN_USORT_FEW_READS;
         return fail(c, HPN_E_DOMAIN, "%llu reads counted: the reference divides by %llu / 10 = 0 behind its first record", (unsigned long long)e,
                     (unsigned long long)e);
@@ -202,17 +157,17 @@ int hpn_fastq_usort_finish(hpn_ctx *c, hpn_usort_result *res)
     const uint32_t *first = (const uint32_t *)u->first.p, *count = (const uint32_t *)u->count.p;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTally], c->stream));
     // (strLen is set in front of the pair test, :129: the mate-0 record at which the pairs stop still counts)
-    HPN_HIP(c, launch_usort_seqlen(d0, res->unmatched >= 0 ? N + 1u : N, u->d_info, c->stream));
+    HPN_HIP(c, launch_usort_seqlen(d0, res->unmatched >= 0 ? N + 1u : N, uniq_kinfo(u), c->stream));
     HPN_HIP(c, launch_usort_djb64(t0, d0, t1, d1, paired, first, U, (uint64_t *)q->djb64.p, c->stream));
     HPN_HIP(c, launch_usort_bucket(t0, d0, t1, d1, paired, first, (const uint32_t *)u->rank.p, count, (const uint64_t *)q->djb64.p, U, S, key, val,
-                                   u->d_info, c->stream));
-    if ((rc = uniq_fetch_info(c, u)) != HPN_OK) return rc;
-    res->max_count = u->h_info[kUsMaxCount];
-    res->seq_len = q->seq_len = u->h_info[kUsSeqLen];
-    if (u->h_info[kUsLongKey] || u->h_info[kUsShortKey]) {
-        u->open = false;
-        res->no_answer = u->h_info[kUsLongKey] ? HPN_USORT_LONG_KEY : HPN_USORT_SHORT_KEY;
-        return u->h_info[kUsLongKey] ? fail(c, HPN_E_DOMAIN, "a pair's joined sequences have more than 1023 bytes: the reference's key buffer holds 1024")
+                                   uniq_kinfo(u), c->stream));
+    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    res->max_count = u->s.h_info[kUiBase + kUsMaxCount];
+    res->seq_len = q->seq_len = u->s.h_info[kUiBase + kUsSeqLen];
+    if (u->s.h_info[kUiBase + kUsLongKey] || u->s.h_info[kUiBase + kUsShortKey]) {
+        u->s.open = false;
+        res->no_answer = u->s.h_info[kUiBase + kUsLongKey] ? HPN_USORT_LONG_KEY : HPN_USORT_SHORT_KEY;
+        return u->s.h_info[kUiBase + kUsLongKey] ? fail(c, HPN_E_DOMAIN, "a pair's joined sequences have more than 1023 bytes: the reference's key buffer holds 1024")
                                      : fail(c, HPN_E_DOMAIN, "a pair's joined sequences have fewer than the %u bytes of the first read: the reference prints from behind the key", q->seq_len);
     }
     // the walk: slots ascending, every chain newest first; then count descending over the digits that can differ
@@ -221,7 +176,7 @@ int hpn_fastq_usort_finish(hpn_ctx *c, hpn_usort_result *res)
     if ((rc = uniq_sort(c, u, key, val, U, 0, bits_of(res->max_count))) != HPN_OK) return rc;
     HPN_HIP(c, hipMemcpyAsync(q->list.p, val, (size_t)U * 4, hipMemcpyDeviceToDevice, c->stream));
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTally], c->stream));
-    u->finished = true;
+    u->s.finished = true;
     for (int k = paired; k >= 0; --k) {   // (mate 0 last: its text stays built for the first hpn_fastq_usort_write)
         if ((rc = build_output(c, q, k)) != HPN_OK) return rc;
         res->out_bytes[k] = u->out_total;
@@ -235,19 +190,11 @@ int hpn_fastq_usort_write(hpn_ctx *c, int mate, uint64_t offset, void *out, uint
     if (!c || !written) return HPN_E_ARG;
     hpn_usort_state *q = c->us;
     hpn_uniq_state *u = q ? &q->g : nullptr;
-    if (!u || !u->finished) return fail(c, HPN_E_STATE, "hpn_fastq_usort_finish first");
-    if (mate < 0 || mate > u->paired) return fail(c, HPN_E_ARG, "mate %d of a %s session", mate, u->paired ? "paired" : "single-end");
-    HPN_HIP(c, hipSetDevice(c->device));
-    *written = 0;
     int rc;
+    if ((rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_usort", written)) != HPN_OK) return rc;
+    if (mate < 0 || mate > u->paired) return fail(c, HPN_E_ARG, "mate %d of a %s session", mate, u->paired ? "paired" : "single-end");
     if (u->cached_mate != mate && (rc = build_output(c, q, mate)) != HPN_OK) return rc;
-    if (offset > u->out_total) return fail(c, HPN_E_ARG, "offset %llu beyond the output's %llu bytes", (unsigned long long)offset, (unsigned long long)u->out_total);
-    const uint64_t n = u->out_total - offset < cap ? u->out_total - offset : cap;
-    if (n && !out) return fail(c, HPN_E_ARG, "out is NULL");
-    if (n) HPN_HIP(c, hipMemcpyAsync(out, (const uint8_t *)u->out.p + offset, n, hipMemcpyDefault, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    *written = n;
-    return HPN_OK;
+    return session_write_slice(c, u->out, u->out_total, offset, out, cap, written);
 }
 
 }  // extern "C"

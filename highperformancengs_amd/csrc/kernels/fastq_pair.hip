@@ -30,15 +30,10 @@
 // Bound: the join is latency -- dependent probes of names that are scattered over the store; everything else streams the
 // descriptors once and the text once (docs/kernels/fastq_pair.md has the bytes and the expectation).
 #include "pair_cmp.hpp"
+#include "sort_desc.hpp"
 #include "text_common.hpp"
 
 namespace hpn {
-
-struct SortDesc {   // kernels/fastq_sort.hip (k_sort_frame writes them)
-    u64 off;
-    uint16_t nlen, slen, qlen, qrel;
-};
-static_assert(sizeof(SortDesc) == 16, "SortDesc is one 16-byte load");
 
 constexpr int kPairTeamsPerWave = kWave / kPairTeam;
 constexpr uint32_t kPairTeamsPerBlock = kTxtThreads / kPairTeam;

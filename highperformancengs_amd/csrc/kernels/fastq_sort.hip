@@ -26,15 +26,10 @@
 // Bound: HBM.  Round 0 and the output touch every record; on reads, round 1 touches nearly all of them once more (4^6
 // prefixes) and round 2 a few thousand.  The scattered loads (key0: descriptor then text; word, equal: text) are issued for
 // several records per lane before the first is used.
+#include "sort_desc.hpp"
 #include "text_common.hpp"
 
 namespace hpn {
-
-struct SortDesc {
-    u64 off;                           // where the record's name line starts in the store
-    uint16_t nlen, slen, qlen, qrel;   // name, sequence, quality as the reference keeps them; quality's offset from `off`
-};
-static_assert(sizeof(SortDesc) == 16, "SortDesc is one 16-byte load");
 
 constexpr uint32_t kSortItems = 4;   // records per lane where the loads are scattered
 

@@ -21,15 +21,10 @@
 //
 // Bound: HBM.  Pack reads the sequence bytes once (and 16 + 8 bytes of descriptor and offset per record) and writes a quarter
 // of them; unpack reads a quarter of what it writes (docs/kernels/twobit.md).
+#include "sort_desc.hpp"
 #include "text_common.hpp"
 
 namespace hpn {
-
-struct SortDesc {   // kernels/fastq_sort.hip (k_sort_frame writes them)
-    u64 off;
-    uint16_t nlen, slen, qlen, qrel;
-};
-static_assert(sizeof(SortDesc) == 16, "SortDesc is one 16-byte load");
 
 __global__ __launch_bounds__(256) void k_pack_sizes(const SortDesc *__restrict__ desc, uint32_t n, uint32_t *__restrict__ size)
 {

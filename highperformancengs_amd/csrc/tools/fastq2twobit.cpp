@@ -18,11 +18,11 @@
 
 #include <string>
 
-#include "../host/mem_lines.hpp"
-#include "../host/report.hpp"
-#include "../host/text_feed.hpp"
+#include "../host/store_tool.hpp"
 
 using namespace hpn;
+
+static const char kTool[] = "fastq2twobit";
 
 static void usage(const char *prog)
 {
@@ -39,79 +39,6 @@ static void usage(const char *prog)
             "   [-h] This helpful help screen.                                   [option]\n\n",
             prog, prog);
     exit(1);
-}
-
-[[noreturn]] static void refuse(const char *path, const char *why)
-{
-    fprintf(stderr, "fastq2twobit: %s: %s (the reference has no answer there)\n", path, why);
-    leave(2);
-}
-
-static bool add_chunk(hpn_ctx *ctx, const void *text, uint64_t n, bool last, uint64_t *records)
-{
-    hpn_sort_info si;
-    const int rc = hpn_twobit_pack_add(ctx, text, n, last, &si);
-    if (rc == HPN_E_CAPACITY) {
-        fprintf(stderr, "fastq2twobit: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
-        leave(2);
-    }
-    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_twobit_pack_add");
-    *records += si.n_records;
-    return si.irregular == 0;
-}
-
-// The file's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
-struct FileSink {
-    hpn_ctx *ctx;
-    uint64_t *records;
-    void route_begins() {}
-    bool start_over() { return false; }   // the session is void: the caller begins a new one
-    bool chunk(const void *text, uint64_t n, bool last) { return add_chunk(ctx, text, n, last, records); }
-};
-
-// A file into the session on the device.  false: the text is not regular (or a route gave up half way) -- the session is void
-// and the caller frames the file on the host.
-static bool device_feed(hpn_ctx *ctx, const char *path, uint64_t *records)
-{
-    FileSink sink{ctx, records};
-    const FeedEnd end = feed_fastq_file(ctx, path, "fastq2twobit", sink);
-    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-    return end == FeedEnd::kDone;
-}
-
-// readNextNode (fastq2twobit.c, the same as gzfastq_sort.c:143-165) over the stream in memory: the gzeof test sits behind the
-// FIRST gzgets only.  The records go out as canonical text -- the fields as strlen sees them, every line closed -- which the
-// device frames like any regular chunk.  Refuses what the reference crashes on.
-static void host_feed(hpn_ctx *ctx, const char *path, const std::string &mem, uint64_t *records)
-{
-    MemLines in(mem);
-    std::string text;
-    const size_t kFlush = (size_t)8 << 20;
-    auto field = [&](bool have, const char *p, size_t n) {   // what strlen sees, without its last byte
-        if (!have) refuse(path, "the file ends inside a record");
-        if (n == (size_t)kLineBuf - 1 && p[n - 1] != '\n') refuse(path, "line of 1023 or more characters");
-        const size_t l = strnlen(p, n);
-        if (!l) refuse(path, "line that starts with a NUL byte");
-        text.append(p, l - 1).push_back('\n');
-    };
-    for (;;) {
-        const char *p;
-        size_t n;
-        bool have = in.gets(&p, &n);
-        if (in.past) break;
-        field(have, p, n);
-        have = in.gets(&p, &n);
-        field(have, p, n);
-        if (!in.gets(&p, &n)) refuse(path, "the file ends inside a record");
-        text.append("+\n");
-        have = in.gets(&p, &n);
-        field(have, p, n);
-        if (text.size() >= kFlush) {
-            if (!add_chunk(ctx, text.data(), text.size(), false, records)) refuse(path, "records too short for the device's line index");
-            text.clear();
-        }
-    }
-    if (!add_chunk(ctx, text.data(), text.size(), true, records)) refuse(path, "records too short for the device's line index");
 }
 
 int main(int argc, char *argv[])
@@ -141,26 +68,23 @@ int main(int argc, char *argv[])
     std::string mem;
     uint64_t records = 0;
     bool done = false;
-    if (is_stdin && !slurp_stream(infile, mem)) refuse(infile, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+    auto add = [&](const void *text, uint64_t n, bool last) {
+        hpn_sort_info si = {};
+        const int arc = hpn_twobit_pack_add(ctx, text, n, last, &si);
+        records += si.n_records;
+        return chunk_taken(ctx, kTool, "hpn_twobit_pack_add", arc, si.irregular);
+    };
+    if (is_stdin) slurp_or_refuse(kTool, infile, mem);
     if (text_path_enabled()) {
         if ((rc = hpn_twobit_pack_begin(ctx, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_twobit_pack_begin");
-        if (is_stdin) {
-            const uint64_t piece = text_chunk_bytes();
-            uint64_t at = 0;
-            do {
-                const uint64_t k = mem.size() - at < piece ? mem.size() - at : piece;
-                done = add_chunk(ctx, mem.data() + at, k, at + k == mem.size(), &records);
-                at += k;
-            } while (done && at < mem.size());
-        } else {
-            done = device_feed(ctx, infile, &records);
-        }
+        done = is_stdin ? memory_feed(mem, add) : device_feed(ctx, kTool, infile, add);
     }
     if (!done) {
-        if (!is_stdin && !slurp_stream(infile, mem)) refuse(infile, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+        if (!is_stdin) slurp_or_refuse(kTool, infile, mem);
         records = 0;
         if ((rc = hpn_twobit_pack_begin(ctx, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_twobit_pack_begin");
-        host_feed(ctx, infile, mem, &records);
+        // readNextNode (fastq2twobit.c, the same as gzfastq_sort.c:143-165): the fields as strlen sees them
+        if (const char *why = canonical_feed(mem, FieldRule::kStrlen, false, add)) refuse(kTool, infile, why);
     }
     const long long fed = usec();
     static hpn_twobit_result res;
@@ -175,7 +99,7 @@ int main(int argc, char *argv[])
     fprintf(stderr, "done read file at %.3f s\nlist count: %d\n", (double)(fed - begin) / CLOCKS_PER_SEC, (int)res.n_records);
     fprintf(stderr, "done dump_array at %.3f s\n", (double)(packed - begin) / CLOCKS_PER_SEC);
     fprintf(stderr, "done sort file at %.3f s\n", (double)(packed - begin) / CLOCKS_PER_SEC);
-    write_device_output(ctx, "fastq2twobit", outfile, by_name ? "_sort_by_name.fq" : "_sort_by_seq.fq", res.out_bytes, text_slice_bytes((uint64_t)32 << 20),
+    write_device_output(ctx, kTool, outfile, by_name ? "_sort_by_name.fq" : "_sort_by_seq.fq", res.out_bytes, text_slice_bytes((uint64_t)32 << 20),
                         [&](uint64_t at, void *buf, uint64_t cap, uint64_t *got) {
                             const int wrc = hpn_twobit_pack_write(ctx, at, buf, cap, got);
                             if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_twobit_pack_write");

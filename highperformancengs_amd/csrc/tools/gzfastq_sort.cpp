@@ -18,11 +18,11 @@
 
 #include <string>
 
-#include "../host/fastq_reader.hpp"
-#include "../host/report.hpp"
-#include "../host/text_feed.hpp"
+#include "../host/store_tool.hpp"
 
 using namespace hpn;
+
+static const char kTool[] = "gzfastq_sort";
 
 static void usage(const char *prog)
 {
@@ -43,12 +43,6 @@ static void usage(const char *prog)
     exit(1);
 }
 
-[[noreturn]] static void refuse(const char *path, const char *why)
-{
-    fprintf(stderr, "gzfastq_sort: %s: %s (the reference has no answer there)\n", path, why);
-    leave(2);
-}
-
 // str2unsigned_long (gzfastq_sort.c:71-83): the leading digits, modulo 2^64
 static unsigned long parse_reads_num(const char *str)
 {
@@ -60,75 +54,6 @@ static unsigned long parse_reads_num(const char *str)
     for (; *str >= '0' && *str <= '9'; ++str) v = v * 10 + (unsigned long)(*str - '0');
     return v;
 }
-
-static bool add_chunk(hpn_ctx *ctx, const void *text, uint64_t n, bool last, uint64_t *records)
-{
-    hpn_sort_info si;
-    const int rc = hpn_fastq_sort_add(ctx, text, n, last, &si);
-    if (rc == HPN_E_CAPACITY) {
-        fprintf(stderr, "gzfastq_sort: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
-        leave(2);
-    }
-    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_sort_add");
-    *records += si.n_records;
-    return si.irregular == 0;
-}
-
-// The file's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
-struct FileSink {
-    hpn_ctx *ctx;
-    uint64_t *records;
-    void route_begins() {}
-    bool start_over() { return false; }   // the session is void: the caller begins a new one
-    bool chunk(const void *text, uint64_t n, bool last) { return add_chunk(ctx, text, n, last, records); }
-};
-
-// A file into the session on the device.  false: the text is not regular (or a route gave up half way) -- the session is void
-// and the caller frames the file on the host.
-static bool device_feed(hpn_ctx *ctx, const char *path, uint64_t *records)
-{
-    FileSink sink{ctx, records};
-    const FeedEnd end = feed_fastq_file(ctx, path, "gzfastq_sort", sink);
-    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-    return end == FeedEnd::kDone;
-}
-
-// the whole inflated stream in memory (standard input, which cannot be read twice; a file whose text is not regular)
-static void slurp(const char *path, std::string &mem)
-{
-    InStream in = open_input_stream(path);
-    std::vector<char> buf((size_t)1 << 20);
-    for (;;) {
-        const int k = in.read(buf.data(), (unsigned)buf.size());
-        if (k <= 0) break;
-        mem.append(buf.data(), (size_t)k);
-    }
-    const bool damaged = in.damaged();
-    in.close();
-    if (damaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-}
-
-// gzgets(file, buf, 1024) and gzeof over the stream in memory
-struct MemLines {
-    const std::string &d;
-    size_t pos = 0;
-    bool past = false;
-    explicit MemLines(const std::string &s) : d(s) {}
-    bool gets(const char **p, size_t *n)
-    {
-        if (pos >= d.size()) {
-            past = true;
-            return false;
-        }
-        const size_t room = d.size() - pos < (size_t)kLineBuf - 1 ? d.size() - pos : (size_t)kLineBuf - 1;
-        const void *nl = memchr(d.data() + pos, '\n', room);
-        size_t k = nl ? (size_t)((const char *)nl - (d.data() + pos)) + 1 : room;
-        if (!nl && pos + k == d.size() && k < (size_t)kLineBuf - 1) past = true;
-        *p = d.data() + pos, *n = k;
-        pos += k;
-        return true;
-    }
-};
 
 // count_read (gzfastq_sort.c:185-198)
 static unsigned long count_reads(const std::string &mem)
@@ -142,41 +67,6 @@ static unsigned long count_reads(const std::string &mem)
         ++reads;
     }
     return reads;
-}
-
-// readNextNode (gzfastq_sort.c:143-165) over the stream in memory: the gzeof test sits behind the FIRST gzgets only.  The
-// records go out as canonical text -- the fields as strlen sees them, every line closed -- which the device frames like any
-// regular chunk.  Refuses what the reference crashes on.
-static void host_feed(hpn_ctx *ctx, const char *path, const std::string &mem, uint64_t *records)
-{
-    MemLines in(mem);
-    std::string text;
-    const size_t kFlush = (size_t)8 << 20;
-    auto field = [&](bool have, const char *p, size_t n) {   // what strlen sees, without its last byte
-        if (!have) refuse(path, "the file ends inside a record");
-        if (n == (size_t)kLineBuf - 1 && p[n - 1] != '\n') refuse(path, "line of 1023 or more characters");
-        const size_t l = strnlen(p, n);
-        if (!l) refuse(path, "line that starts with a NUL byte");
-        text.append(p, l - 1).push_back('\n');
-    };
-    for (;;) {
-        const char *p;
-        size_t n;
-        bool have = in.gets(&p, &n);
-        if (in.past) break;
-        field(have, p, n);
-        have = in.gets(&p, &n);
-        field(have, p, n);
-        if (!in.gets(&p, &n)) refuse(path, "the file ends inside a record");
-        text.append("+\n");
-        have = in.gets(&p, &n);
-        field(have, p, n);
-        if (text.size() >= kFlush) {
-            if (!add_chunk(ctx, text.data(), text.size(), false, records)) refuse(path, "records too short for the device's line index");
-            text.clear();
-        }
-    }
-    if (!add_chunk(ctx, text.data(), text.size(), true, records)) refuse(path, "records too short for the device's line index");
 }
 
 int main(int argc, char *argv[])
@@ -210,31 +100,28 @@ int main(int argc, char *argv[])
     uint64_t records = 0;
     bool done = false, counted = false;
     unsigned long total_reads = 0;
-    if (is_stdin) slurp(infile, mem);
+    auto add = [&](const void *text, uint64_t n, bool last) {
+        hpn_sort_info si = {};
+        const int arc = hpn_fastq_sort_add(ctx, text, n, last, &si);
+        records += si.n_records;
+        return chunk_taken(ctx, kTool, "hpn_fastq_sort_add", arc, si.irregular);
+    };
+    if (is_stdin) slurp_or_refuse(kTool, infile, mem);
     if (!reads_num && !rewindable) {   // the count consumed the pipe: the reference then reads nothing
         total_reads = count_reads(mem), counted = true;
         mem.clear();
     }
     if (text_path_enabled()) {
         if ((rc = hpn_fastq_sort_begin(ctx, by_name, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_sort_begin");
-        if (is_stdin) {
-            const uint64_t piece = text_chunk_bytes();
-            uint64_t at = 0;
-            do {
-                const uint64_t k = mem.size() - at < piece ? mem.size() - at : piece;
-                done = add_chunk(ctx, mem.data() + at, k, at + k == mem.size(), &records);
-                at += k;
-            } while (done && at < mem.size());
-        } else {
-            done = device_feed(ctx, infile, &records);
-        }
+        done = is_stdin ? memory_feed(mem, add) : device_feed(ctx, kTool, infile, add);
     }
     if (!done) {
-        if (!is_stdin) slurp(infile, mem);
+        if (!is_stdin) slurp_or_refuse(kTool, infile, mem);
         if (!reads_num && !counted) total_reads = count_reads(mem), counted = true;
         records = 0;
         if ((rc = hpn_fastq_sort_begin(ctx, by_name, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_sort_begin");
-        host_feed(ctx, infile, mem, &records);
+        // readNextNode (gzfastq_sort.c:143-165): the fields as strlen sees them
+        if (const char *why = canonical_feed(mem, FieldRule::kStrlen, false, add)) refuse(kTool, infile, why);
     }
     if (reads_num && reads_num < records) {
         fprintf(stderr, "gzfastq_sort: -r %lu is below the file's %llu reads (the reference has no answer there: it writes behind its array)\n", reads_num,
@@ -253,7 +140,7 @@ int main(int argc, char *argv[])
     fprintf(stderr, "done read file at %.3f s\n", (double)(fed - begin) / CLOCKS_PER_SEC);
     const long long ordered = usec();
     fprintf(stderr, "done qsort file at %.3f s\n", (double)(ordered - begin) / CLOCKS_PER_SEC);
-    write_device_output(ctx, "gzfastq_sort", outfile, by_name ? "_sort_by_name.fq" : "_sort_by_seq.fq", res.out_bytes, text_slice_bytes((uint64_t)32 << 20),
+    write_device_output(ctx, kTool, outfile, by_name ? "_sort_by_name.fq" : "_sort_by_seq.fq", res.out_bytes, text_slice_bytes((uint64_t)32 << 20),
                         [&](uint64_t at, void *buf, uint64_t cap, uint64_t *got) {
                             const int wrc = hpn_fastq_sort_write(ctx, at, buf, cap, got);
                             if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_fastq_sort_write");

@@ -20,11 +20,11 @@
 
 #include <string>
 
-#include "../host/fastq_reader.hpp"
-#include "../host/report.hpp"
-#include "../host/text_feed.hpp"
+#include "../host/store_tool.hpp"
 
 using namespace hpn;
+
+static const char kTool[] = "gzfastq_uniq";
 
 static void usage(const char *prog)
 {
@@ -42,39 +42,14 @@ static void usage(const char *prog)
     exit(1);
 }
 
-[[noreturn]] static void refuse(const char *path, const char *why)
+// one mate's `add` (host/store_tool.hpp)
+static auto add_to(hpn_ctx *ctx, int mate)
 {
-    fprintf(stderr, "gzfastq_uniq: %s: %s (the reference has no answer there)\n", path, why);
-    leave(2);
-}
-
-// One mate's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
-struct MateSink {
-    hpn_ctx *ctx;
-    int mate;
-    void route_begins() {}
-    bool start_over() { return false; }   // the session is void: the caller begins a new one
-    bool chunk(const void *text, uint64_t n, bool last)
-    {
-        hpn_uniq_info ui;
+    return [ctx, mate](const void *text, uint64_t n, bool last) {
+        hpn_uniq_info ui = {};
         const int rc = hpn_fastq_uniq_add(ctx, mate, text, n, last, &ui);
-        if (rc == HPN_E_CAPACITY) {
-            fprintf(stderr, "gzfastq_uniq: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
-            leave(2);
-        }
-        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniq_add");
-        return ui.irregular == 0;
-    }
-};
-
-// One mate's file into the session on the device.  false: the text is not regular (or a route gave up half way) -- the session
-// is void and the caller frames the files on the host.
-static bool device_feed(hpn_ctx *ctx, int mate, const char *path)
-{
-    MateSink sink{ctx, mate};
-    const FeedEnd end = feed_fastq_file(ctx, path, "gzfastq_uniq", sink);
-    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-    return end == FeedEnd::kDone;
+        return chunk_taken(ctx, kTool, "hpn_fastq_uniq_add", rc, ui.irregular);
+    };
 }
 
 // readNextNode (gzfastq_uniq.c:170-192) with the exact gzgets emulation: the gzeof test sits behind the FIRST gzgets only.
@@ -91,18 +66,18 @@ struct HostReader {
     {
         size_t n1 = 0, n2 = 0, n3 = 0, n4 = 0;
         char *first = src.gets(name, kLineBuf, &n1);
-        if (in.damaged()) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+        if (in.damaged()) refuse(kTool, path, kWhyDamaged);
         if (src.eof()) return false;
         if (!first || !src.gets(seq, kLineBuf, &n2) || !src.gets(plus, kLineBuf, &n3) || !src.gets(qual, kLineBuf, &n4)) {
-            if (in.damaged()) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-            refuse(path, "the file ends inside a record");
+            if (in.damaged()) refuse(kTool, path, kWhyDamaged);
+            refuse(kTool, path, "the file ends inside a record");
         }
         if (name[n1 - 1] != '\n' || seq[n2 - 1] != '\n' || plus[n3 - 1] != '\n' || (n4 == (size_t)kLineBuf - 1 && qual[n4 - 1] != '\n'))
-            refuse(path, "line of 1023 or more characters");
+            refuse(kTool, path, "line of 1023 or more characters");
         const size_t l1 = strlen(name), l2 = strlen(seq), l4 = strlen(qual);
-        if (!l1 || !l2 || !l4) refuse(path, "line that starts with a NUL byte");
+        if (!l1 || !l2 || !l4) refuse(kTool, path, "line that starts with a NUL byte");
         name[l1 - 1] = 0, seq[l2 - 1] = 0, qual[l4 - 1] = 0;   // :174, :179, :185
-        if (l4 + 1 < l2) refuse(path, "quality line two or more bytes shorter than its sequence");
+        if (l4 + 1 < l2) refuse(kTool, path, "quality line two or more bytes shorter than its sequence");
         text.append(name, l1 - 1).append("\n").append(seq, l2 - 1).append("\n+\n").append(qual, l4 - 1).append("\n");
         return true;
     }
@@ -119,14 +94,7 @@ static void host_feed(hpn_ctx *ctx, const char *read1, const char *read2, HostEr
     HostReader r1(read1);
     std::string t1, t2;
     auto flush = [&](int mate, std::string &t, bool last) {
-        hpn_uniq_info ui;
-        const int rc = hpn_fastq_uniq_add(ctx, mate, t.data(), t.size(), last, &ui);
-        if (rc == HPN_E_CAPACITY) {
-            fprintf(stderr, "gzfastq_uniq: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
-            leave(2);
-        }
-        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniq_add");
-        if (ui.irregular) refuse(mate ? read2 : read1, "records too short for the device's line index");
+        if (!add_to(ctx, mate)(t.data(), t.size(), last)) refuse(kTool, mate ? read2 : read1, kWhyTooShort);
         t.clear();
     };
     const size_t kFlush = (size_t)8 << 20;
@@ -192,7 +160,7 @@ int main(int argc, char *argv[])
     HostError herr;
     if (text_path_enabled()) {
         if ((rc = hpn_fastq_uniq_begin(ctx, read2 != nullptr, 0, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniq_begin");
-        done = device_feed(ctx, 0, read1) && (!read2 || device_feed(ctx, 1, read2));
+        done = device_feed(ctx, kTool, read1, add_to(ctx, 0)) && (!read2 || device_feed(ctx, kTool, read2, add_to(ctx, 1)));
     }
     if (!done) {
         if ((rc = hpn_fastq_uniq_begin(ctx, read2 != nullptr, 0, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniq_begin");
@@ -209,7 +177,7 @@ int main(int argc, char *argv[])
     fprintf(stderr, "Finished load hash at %.3f s\n", (double)(usec() - begin) / CLOCKS_PER_SEC);
     const long long grouped = usec();
     auto write_output = [&](int which, int mate, const char *suffix) {
-        write_device_output(ctx, "gzfastq_uniq", outfile, suffix, res.out_bytes[mate], text_slice_bytes((uint64_t)32 << 20),
+        write_device_output(ctx, kTool, outfile, suffix, res.out_bytes[mate], text_slice_bytes((uint64_t)32 << 20),
                             [&](uint64_t at, void *buf, uint64_t cap, uint64_t *got) {
                                 const int wrc = hpn_fastq_uniq_write(ctx, which, mate, at, buf, cap, got);
                                 if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_fastq_uniq_write");

@@ -19,12 +19,11 @@
 
 #include <string>
 
-#include "../host/fastq_reader.hpp"
-#include "../host/mem_lines.hpp"
-#include "../host/report.hpp"
-#include "../host/text_feed.hpp"
+#include "../host/store_tool.hpp"
 
 using namespace hpn;
+
+static const char kTool[] = "gzfastq_uniqQ";
 
 static void usage(const char *prog)
 {
@@ -41,82 +40,6 @@ static void usage(const char *prog)
             "   [-h]        = This helpful help screen.                            [option]\n\n",
             prog);
     exit(1);
-}
-
-[[noreturn]] static void refuse(const char *path, const char *why)
-{
-    fprintf(stderr, "gzfastq_uniqQ: %s: %s (the reference has no answer there)\n", path, why);
-    leave(2);
-}
-
-static bool add_chunk(hpn_ctx *ctx, const void *text, uint64_t n, bool last)
-{
-    hpn_uniq_info ui;
-    const int rc = hpn_fastq_uniqq_add(ctx, text, n, last, &ui);
-    if (rc == HPN_E_CAPACITY) {
-        fprintf(stderr, "gzfastq_uniqQ: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
-        leave(2);
-    }
-    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniqq_add");
-    return ui.irregular == 0;
-}
-
-// The file's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
-struct FileSink {
-    hpn_ctx *ctx;
-    void route_begins() {}
-    bool start_over() { return false; }   // the session is void: the caller begins a new one
-    bool chunk(const void *text, uint64_t n, bool last) { return add_chunk(ctx, text, n, last); }
-};
-
-// A file into the session on the device.  false: the text is not regular (or a route gave up half way) -- the session is void
-// and the caller frames the file on the host.
-static bool device_feed(hpn_ctx *ctx, const char *path)
-{
-    FileSink sink{ctx};
-    const FeedEnd end = feed_fastq_file(ctx, path, "gzfastq_uniqQ", sink);
-    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-    return end == FeedEnd::kDone;
-}
-
-// the whole inflated stream in memory (standard input, which cannot be read twice; a file whose text is not regular)
-static void slurp(const char *path, std::string &mem)
-{
-    if (!slurp_stream(path, mem)) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-}
-
-// readNextNode (gzfastq_uniqQ.c:181-203) over the stream in memory: the gzeof test sits behind the FIRST gzgets only.  The
-// records go out as canonical text -- every line without its last byte and closed -- which the device frames like any
-// regular chunk.  Refuses what the reference crashes on.
-static void host_feed(hpn_ctx *ctx, const char *path, const std::string &mem)
-{
-    MemLines in(mem);
-    std::string text;
-    const size_t kFlush = (size_t)8 << 20;
-    auto field = [&](bool have, const char *p, size_t n) {   // the line without its last byte
-        if (!have) refuse(path, "the file ends inside a record");
-        if (n == (size_t)kLineBuf - 1 && p[n - 1] != '\n') refuse(path, "line of 1023 or more characters");
-        if (memchr(p, 0, n)) refuse(path, "NUL byte in a line");
-        text.append(p, n - 1).push_back('\n');
-    };
-    for (;;) {
-        const char *p;
-        size_t n;
-        bool have = in.gets(&p, &n);
-        if (in.past) break;
-        field(have, p, n);
-        have = in.gets(&p, &n);
-        field(have, p, n);
-        if (!in.gets(&p, &n)) refuse(path, "the file ends inside a record");
-        text.append("+\n");
-        have = in.gets(&p, &n);
-        field(have, p, n);
-        if (text.size() >= kFlush) {
-            if (!add_chunk(ctx, text.data(), text.size(), false)) refuse(path, "records too short for the device's line index");
-            text.clear();
-        }
-    }
-    if (!add_chunk(ctx, text.data(), text.size(), true)) refuse(path, "records too short for the device's line index");
 }
 
 int main(int argc, char *argv[])
@@ -148,25 +71,21 @@ int main(int argc, char *argv[])
 
     std::string mem;
     bool done = false;
-    if (is_stdin) slurp(read1, mem);
+    auto add = [&](const void *text, uint64_t n, bool last) {
+        hpn_uniq_info ui = {};
+        const int arc = hpn_fastq_uniqq_add(ctx, text, n, last, &ui);
+        return chunk_taken(ctx, kTool, "hpn_fastq_uniqq_add", arc, ui.irregular);
+    };
+    if (is_stdin) slurp_or_refuse(kTool, read1, mem);
     if (text_path_enabled()) {
         if ((rc = hpn_fastq_uniqq_begin(ctx, 0, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniqq_begin");
-        if (is_stdin) {
-            const uint64_t piece = text_chunk_bytes();
-            uint64_t at = 0;
-            do {
-                const uint64_t k = mem.size() - at < piece ? mem.size() - at : piece;
-                done = add_chunk(ctx, mem.data() + at, k, at + k == mem.size());
-                at += k;
-            } while (done && at < mem.size());
-        } else {
-            done = device_feed(ctx, read1);
-        }
+        done = is_stdin ? memory_feed(mem, add) : device_feed(ctx, kTool, read1, add);
     }
     if (!done) {
-        if (!is_stdin) slurp(read1, mem);
+        if (!is_stdin) slurp_or_refuse(kTool, read1, mem);
         if ((rc = hpn_fastq_uniqq_begin(ctx, 0, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_uniqq_begin");
-        host_feed(ctx, read1, mem);
+        // readNextNode (gzfastq_uniqQ.c:181-203): every line without its last byte
+        if (const char *why = canonical_feed(mem, FieldRule::kLine, false, add)) refuse(kTool, read1, why);
     }
     const long long fed = usec();
     static hpn_uniqq_result res;
@@ -177,7 +96,7 @@ int main(int argc, char *argv[])
     fprintf(stderr, "Finished load hash at %.3f s\n", (double)(usec() - begin) / CLOCKS_PER_SEC);
     const long long grouped = usec();
     const int which = by_count ? HPN_UNIQQ_COUNT_ORDER : HPN_UNIQQ_KEY_ORDER;
-    write_device_output(ctx, "gzfastq_uniqQ", outfile, "_sortKeyUniq.fq", res.out_bytes, text_slice_bytes((uint64_t)32 << 20),
+    write_device_output(ctx, kTool, outfile, "_sortKeyUniq.fq", res.out_bytes, text_slice_bytes((uint64_t)32 << 20),
                         [&](uint64_t at, void *buf, uint64_t cap, uint64_t *got) {
                             const int wrc = hpn_fastq_uniqq_write(ctx, which, at, buf, cap, got);
                             if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_fastq_uniqq_write");

@@ -23,13 +23,11 @@
 
 #include <string>
 
-#include "../host/fastq_reader.hpp"
-#include "../host/gz_writer.hpp"
-#include "../host/mem_lines.hpp"
-#include "../host/report.hpp"
-#include "../host/text_feed.hpp"
+#include "../host/store_tool.hpp"
 
 using namespace hpn;
+
+static const char kTool[] = "gzfastq_uniq_sort";
 
 static void usage(const char *prog)
 {
@@ -45,120 +43,6 @@ static void usage(const char *prog)
             "   [-h]        = This helpful help screen.                            [option]\n\n",
             prog);
     exit(1);
-}
-
-[[noreturn]] static void refuse(const char *path, const char *why)
-{
-    fprintf(stderr, "gzfastq_uniq_sort: %s: %s (the reference has no answer there)\n", path, why);
-    leave(2);
-}
-
-static bool add_chunk(hpn_ctx *ctx, int mate, const void *text, uint64_t n, bool last)
-{
-    hpn_uniq_info ui;
-    const int rc = hpn_fastq_usort_add(ctx, mate, text, n, last, &ui);
-    if (rc == HPN_E_CAPACITY) {
-        fprintf(stderr, "gzfastq_uniq_sort: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
-        leave(2);
-    }
-    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_usort_add");
-    return ui.irregular == 0;
-}
-
-// One mate's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
-struct MateSink {
-    hpn_ctx *ctx;
-    int mate;
-    void route_begins() {}
-    bool start_over() { return false; }   // the session is void: the caller begins a new one
-    bool chunk(const void *text, uint64_t n, bool last) { return add_chunk(ctx, mate, text, n, last); }
-};
-
-// One mate's file into the session on the device.  false: the text is not regular (or a route gave up half way) -- the session
-// is void and the caller frames the files on the host.
-static bool device_feed(hpn_ctx *ctx, int mate, const char *path)
-{
-    MateSink sink{ctx, mate};
-    const FeedEnd end = feed_fastq_file(ctx, path, "gzfastq_uniq_sort", sink);
-    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-    return end == FeedEnd::kDone;
-}
-
-// the whole inflated stream in memory
-static void slurp(const char *path, std::string &mem)
-{
-    if (!slurp_stream(path, mem)) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-}
-
-// readNextNode (gzfastq_uniq_sort.c:67-88) over one mate's stream in memory: the gzeof test sits behind the FIRST gzgets only.
-// The records go out as canonical text -- every line without its last byte and closed -- which the device frames like any
-// regular chunk; one open line behind the last record, which count_read counts, stays as it is.  Refuses what the reference
-// crashes on.
-static void host_feed(hpn_ctx *ctx, int mate, const char *path)
-{
-    std::string mem;
-    slurp(path, mem);
-    MemLines in(mem);
-    std::string text;
-    const size_t kFlush = (size_t)8 << 20;
-    auto field = [&](bool have, const char *p, size_t n) {   // the line without its last byte
-        if (!have) refuse(path, "the file ends inside a record");
-        if (n == (size_t)kLineBuf - 1 && p[n - 1] != '\n') refuse(path, "line of 1023 or more characters");
-        if (memchr(p, 0, n)) refuse(path, "NUL byte in a line");
-        text.append(p, n - 1).push_back('\n');
-    };
-    for (;;) {
-        const char *p;
-        size_t n;
-        bool have = in.gets(&p, &n);
-        if (in.past) {
-            if (have) {
-                if (memchr(p, 0, n)) refuse(path, "NUL byte in a line");
-                text.append(p, n);
-            }
-            break;
-        }
-        field(have, p, n);
-        have = in.gets(&p, &n);
-        field(have, p, n);
-        if (!in.gets(&p, &n)) refuse(path, "the file ends inside a record");
-        text.append("+\n");
-        have = in.gets(&p, &n);
-        field(have, p, n);
-        if (text.size() >= kFlush) {
-            if (!add_chunk(ctx, mate, text.data(), text.size(), false)) refuse(path, "records too short for the device's line index");
-            text.clear();
-        }
-    }
-    if (!add_chunk(ctx, mate, text.data(), text.size(), true)) refuse(path, "records too short for the device's line index");
-}
-
-// One mate's output through GzWriter.  The file is made here, behind hpn_fastq_usort_finish: a refusal leaves none.
-static double write_output(hpn_ctx *ctx, int mate, const std::string &path, uint64_t total)
-{
-    GzWriter w(path.c_str());
-    if (!w.ok()) {
-        fprintf(stderr, "open file %s failed\n", path.c_str());
-        leave(2);
-    }
-    const uint64_t slice = text_slice_bytes((uint64_t)32 << 20);
-    void *buf = nullptr;
-    if (hpn_host_malloc(ctx, slice, &buf) != HPN_OK) die_hpn(ctx, HPN_E_NOMEM, "gzfastq_uniq_sort");
-    for (uint64_t at = 0; at < total;) {
-        uint64_t got = 0;
-        const int rc = hpn_fastq_usort_write(ctx, mate, at, buf, slice, &got);
-        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_usort_write");
-        if (!got) break;
-        if (!w.write(buf, got)) break;
-        at += got;
-    }
-    if (!w.finish()) {
-        fprintf(stderr, "gzfastq_uniq_sort: writing %s failed (%s)\n", path.c_str(), errno ? strerror(errno) : "short write");
-        unlink(path.c_str());
-        leave(2);
-    }
-    hpn_host_free(ctx, buf);
-    return w.deflate_seconds();
 }
 
 int main(int argc, char *argv[])
@@ -193,20 +77,33 @@ int main(int argc, char *argv[])
     hpn_ctx *ctx = open_tool_ctx();
     int rc;
 
+    const char *reads[2] = {read1, read2};
+    auto add_to = [&](int mate) {
+        return [ctx, mate](const void *text, uint64_t n, bool last) {
+            hpn_uniq_info ui = {};
+            const int arc = hpn_fastq_usort_add(ctx, mate, text, n, last, &ui);
+            return chunk_taken(ctx, kTool, "hpn_fastq_usort_add", arc, ui.irregular);
+        };
+    };
     bool done = false;
     if (text_path_enabled()) {
         if ((rc = hpn_fastq_usort_begin(ctx, read2 != nullptr, 0, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_usort_begin");
-        done = device_feed(ctx, 0, read1) && (!read2 || device_feed(ctx, 1, read2));
+        done = device_feed(ctx, kTool, read1, add_to(0)) && (!read2 || device_feed(ctx, kTool, read2, add_to(1)));
     }
     if (!done) {
         if ((rc = hpn_fastq_usort_begin(ctx, read2 != nullptr, 0, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_usort_begin");
-        host_feed(ctx, 0, read1);
-        if (read2) host_feed(ctx, 1, read2);
+        // readNextNode (gzfastq_uniq_sort.c:67-88): every line without its last byte; one open line behind the last record, which
+        // count_read counts, stays as it is
+        for (int mate = 0; mate < 2 && reads[mate]; ++mate) {
+            std::string mem;
+            slurp_or_refuse(kTool, reads[mate], mem);
+            if (const char *why = canonical_feed(mem, FieldRule::kLine, true, add_to(mate))) refuse(kTool, reads[mate], why);
+        }
     }
     const long long fed = usec();
     static hpn_usort_result res;
     rc = hpn_fastq_usort_finish(ctx, &res);
-    if (rc == HPN_E_DOMAIN && res.no_answer) refuse(read2 && res.no_answer != HPN_USORT_FEW_READS ? read2 : read1, hpn_ctx_last_error(ctx));
+    if (rc == HPN_E_DOMAIN && res.no_answer) refuse(kTool, read2 && res.no_answer != HPN_USORT_FEW_READS ? read2 : read1, hpn_ctx_last_error(ctx));
     if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_usort_finish");
     const unsigned long U = (unsigned long)res.n_unique, N = (unsigned long)res.n_records, e = (unsigned long)res.table_reads;
     const double now = (double)(usec() - begin) / CLOCKS_PER_SEC;
@@ -219,8 +116,17 @@ int main(int argc, char *argv[])
     fprintf(stderr, "hash size: %ld\ntotal reads = %ld\n", (unsigned long)res.hash_size, N);
     fprintf(stderr, "unique reads percentage: %.3f%%\n", (float)U / N * 100);
     const long long grouped = usec();
-    double deflate_s = write_output(ctx, 0, std::string(outfile) + "_1_uniq.fq.gz", res.out_bytes[0]);
-    if (read2) deflate_s += write_output(ctx, 1, std::string(outfile) + "_2_uniq.fq.gz", res.out_bytes[1]);
+    const uint64_t slice = text_slice_bytes((uint64_t)32 << 20);
+    void *buf = nullptr;
+    if (hpn_host_malloc(ctx, slice, &buf) != HPN_OK) die_hpn(ctx, HPN_E_NOMEM, kTool);
+    double deflate_s = 0;
+    for (int mate = 0; mate < 2 && reads[mate]; ++mate)
+        deflate_s += write_gz_output(kTool, std::string(outfile) + (mate ? "_2_uniq.fq.gz" : "_1_uniq.fq.gz"), nullptr, res.out_bytes[mate], buf, slice,
+                                     [&](uint64_t at, void *to, uint64_t cap, uint64_t *got) {
+                                         const int wrc = hpn_fastq_usort_write(ctx, mate, at, to, cap, got);
+                                         if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_fastq_usort_write");
+                                     });
+    hpn_host_free(ctx, buf);
     if (getenv("HPN_TIMING"))
         fprintf(stderr, "[hpn] uniq_sort: reading and keying %.3f s, grouping and ordering %.3f s, formatting, deflating and writing %.3f s (%.3f s of deflate over the threads); %llu hash clashes, largest group %u\n",
                 (double)(fed - begin) / 1e6, (double)(grouped - fed) / 1e6, (double)(usec() - grouped) / 1e6, deflate_s,

@@ -20,12 +20,11 @@
 
 #include <string>
 
-#include "../host/gz_writer.hpp"
-#include "../host/mem_lines.hpp"
-#include "../host/report.hpp"
-#include "../host/text_feed.hpp"
+#include "../host/store_tool.hpp"
 
 using namespace hpn;
+
+static const char kTool[] = "pick_pair";
 
 static const char *const kSuffix[4] = {"_1_PE.fq.gz", "_1_SE.fq.gz", "_2_PE.fq.gz", "_2_SE.fq.gz"};
 
@@ -45,42 +44,6 @@ static void usage(const char *prog)
     exit(1);
 }
 
-[[noreturn]] static void refuse(const char *path, const char *why)
-{
-    fprintf(stderr, "pick_pair: %s: %s (the reference has no answer there)\n", path, why);
-    leave(2);
-}
-
-static bool add_chunk(hpn_ctx *ctx, int mate, const void *text, uint64_t n, bool last)
-{
-    hpn_sort_info si;
-    const int rc = hpn_fastq_pair_add(ctx, mate, text, n, last, &si);
-    if (rc == HPN_E_CAPACITY) {
-        fprintf(stderr, "pick_pair: the reads do not fit into this device's memory: %s\n", hpn_ctx_last_error(ctx));
-        leave(2);
-    }
-    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_pair_add");
-    return si.irregular == 0;
-}
-
-// One mate's text into the session: the sink of feed_fastq_file (host/text_feed.hpp)
-struct MateSink {
-    hpn_ctx *ctx;
-    int mate;
-    void route_begins() {}
-    bool start_over() { return false; }   // the session is void: the host walks
-    bool chunk(const void *text, uint64_t n, bool last) { return add_chunk(ctx, mate, text, n, last); }
-};
-
-// false: the text is not regular (or a route gave up half way)
-static bool device_feed(hpn_ctx *ctx, int mate, const char *path)
-{
-    MateSink sink{ctx, mate};
-    const FeedEnd end = feed_fastq_file(ctx, path, "pick_pair", sink);
-    if (end == FeedEnd::kDamaged) refuse(path, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-    return end == FeedEnd::kDone;
-}
-
 // readNextNode (pick_pair.c) over a stream in memory: four gzgets into a 1024-byte buffer, gzeof tested behind the first; name and
 // sequence lose their last byte, the third line is dropped, the quality line is kept as strdup sees it.
 struct Reader {
@@ -91,9 +54,9 @@ struct Reader {
     Reader(const char *p, const std::string &mem) : path(p), in(mem) {}
     void field(std::string &to, bool got, const char *p, size_t n)
     {
-        if (!got) refuse(path, "the file ends inside a record");
+        if (!got) refuse(kTool, path, "the file ends inside a record");
         const size_t l = strnlen(p, n);
-        if (!l) refuse(path, "line that starts with a NUL byte");
+        if (!l) refuse(kTool, path, "line that starts with a NUL byte");
         to.assign(p, l - 1);
     }
     void next()
@@ -109,7 +72,7 @@ struct Reader {
         got = in.gets(&p, &n);
         field(seq, got, p, n);
         (void)in.gets(&p, &n);
-        if (!in.gets(&p, &n)) refuse(path, "the file ends inside a record");
+        if (!in.gets(&p, &n)) refuse(kTool, path, "the file ends inside a record");
         qual.assign(p, strnlen(p, n));
         have = true;
     }
@@ -134,13 +97,13 @@ static void host_walk(const char *read1, const char *read2, const std::string &m
         a.next();
         b.next();
         while (a.have) {
-            if (!b.have) refuse(read2, "the file runs out in front of the other one");
+            if (!b.have) refuse(kTool, read2, "the file runs out in front of the other one");
             if (name_cmp(a, b) >= 0) break;
             a.emit(out[1]);
             a.next();
         }
         while (b.have) {
-            if (!a.have) refuse(read1, "the file runs out in front of the other one");
+            if (!a.have) refuse(kTool, read1, "the file runs out in front of the other one");
             if (name_cmp(a, b) <= 0) break;
             b.emit(out[3]);
             b.next();
@@ -148,34 +111,6 @@ static void host_walk(const char *read1, const char *read2, const std::string &m
         if (!a.have && !b.have) break;
         if (a.have) a.emit(out[0]);
         if (b.have) b.emit(out[2]);
-    }
-}
-
-// One output through GzWriter, from the session (text == nullptr) or from the host walk's text.  The files are made behind the
-// split: a refusal leaves none.
-static void write_output(hpn_ctx *ctx, int which, const std::string &path, uint64_t total, const std::string *text, void *buf, uint64_t slice)
-{
-    GzWriter w(path.c_str());
-    if (!w.ok()) {
-        fprintf(stderr, "open file %s failed\n", path.c_str());
-        leave(2);
-    }
-    if (text) {
-        if (!text->empty()) (void)w.write(text->data(), text->size());
-    } else {
-        for (uint64_t at = 0; at < total;) {
-            uint64_t got = 0;
-            const int rc = hpn_fastq_pair_write(ctx, which, at, buf, slice, &got);
-            if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_pair_write");
-            if (!got) break;
-            if (!w.write(buf, got)) break;
-            at += got;
-        }
-    }
-    if (!w.finish()) {
-        fprintf(stderr, "pick_pair: writing %s failed (%s)\n", path.c_str(), errno ? strerror(errno) : "short write");
-        unlink(path.c_str());
-        leave(2);
     }
 }
 
@@ -219,7 +154,14 @@ int main(int argc, char *argv[])
     bool done = false;
     if (text_path_enabled() && regular_file(read1) && regular_file(read2)) {
         if ((rc = hpn_fastq_pair_begin(ctx, 0)) != HPN_OK) die_hpn(ctx, rc, "hpn_fastq_pair_begin");
-        if (device_feed(ctx, 0, read1) && device_feed(ctx, 1, read2)) {
+        auto add_to = [&](int mate) {
+            return [ctx, mate](const void *text, uint64_t n, bool last) {
+                hpn_sort_info si = {};
+                const int arc = hpn_fastq_pair_add(ctx, mate, text, n, last, &si);
+                return chunk_taken(ctx, kTool, "hpn_fastq_pair_add", arc, si.irregular);
+            };
+        };
+        if (device_feed(ctx, kTool, read1, add_to(0)) && device_feed(ctx, kTool, read2, add_to(1))) {
             rc = hpn_fastq_pair_finish(ctx, &res);
             if (rc == HPN_OK) done = true, route = res.route == HPN_PAIR_IDENTITY ? "identity" : "join";
             else if (!(rc == HPN_E_DOMAIN && res.unverified)) die_hpn(ctx, rc, "hpn_fastq_pair_finish");
@@ -228,15 +170,20 @@ int main(int argc, char *argv[])
     std::string text[4];
     if (!done) {
         std::string mem1, mem2;
-        if (!slurp_stream(read1, mem1)) refuse(read1, "damaged gzip stream (CRC-32 / ISIZE / data error)");
-        if (!slurp_stream(read2, mem2)) refuse(read2, "damaged gzip stream (CRC-32 / ISIZE / data error)");
+        slurp_or_refuse(kTool, read1, mem1);
+        slurp_or_refuse(kTool, read2, mem2);
         host_walk(read1, read2, mem1, mem2, text);
     }
     const long long split = usec();
     const uint64_t slice = text_slice_bytes((uint64_t)32 << 20);
     void *buf = nullptr;
-    if (done && hpn_host_malloc(ctx, slice, &buf) != HPN_OK) die_hpn(ctx, HPN_E_NOMEM, "pick_pair");
-    for (int w = 0; w < 4; ++w) write_output(ctx, w, std::string(outfile) + kSuffix[w], res.out_bytes[w], done ? nullptr : &text[w], buf, slice);
+    if (done && hpn_host_malloc(ctx, slice, &buf) != HPN_OK) die_hpn(ctx, HPN_E_NOMEM, kTool);
+    for (int w = 0; w < 4; ++w)   // from the session, or the host walk's text
+        write_gz_output(kTool, std::string(outfile) + kSuffix[w], done ? nullptr : &text[w], res.out_bytes[w], buf, slice,
+                        [&](uint64_t at, void *to, uint64_t cap, uint64_t *got) {
+                            const int wrc = hpn_fastq_pair_write(ctx, w, at, to, cap, got);
+                            if (wrc != HPN_OK) die_hpn(ctx, wrc, "hpn_fastq_pair_write");
+                        });
     if (buf) hpn_host_free(ctx, buf);
     fprintf(stderr, "Finished load file at %.3f s\n", (double)(usec() - begin) / CLOCKS_PER_SEC);
     if (getenv("HPN_TIMING"))
