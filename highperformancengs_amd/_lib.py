@@ -96,6 +96,13 @@ class PairResult(C.Structure):
                 ("fail_record", C.c_int64), ("fail_mate", C.c_uint32), ("route", C.c_uint32), ("unverified", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MrleResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64 * 3), ("bad_record", C.c_int64)]
+
+
+MRLE_PACKED, MRLE_TEXT, MRLE_SHARED = 0, 1, 2
+
+
 class TextPiece(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -200,6 +207,10 @@ SYMBOLS = [
     ("hpn_fastq_pair_add", _int, [_vp, _int, _vp, _u64, _int, C.POINTER(SortInfo)]),
     ("hpn_fastq_pair_finish", _int, [_vp, C.POINTER(PairResult)]),
     ("hpn_fastq_pair_write", _int, [_vp, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_mrle_begin", _int, [_vp, _u64]),
+    ("hpn_mrle_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
+    ("hpn_mrle_finish", _int, [_vp, C.POINTER(MrleResult)]),
+    ("hpn_mrle_write", _int, [_vp, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_fastq_text_piece_lines", _int, [_vp, _vp, _u64, _u32, _u64, _int, C.POINTER(TextPiece)]),
     ("hpn_fastq_text_piece_count", _int, [_vp, _u64, _u32, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_piece_trim", _int, [_vp, _u64, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
@@ -261,7 +272,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 7:
+    if L.hpn_abi_version() != 8:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -416,6 +416,34 @@ class Context:
                                           C.byref(got)), "hpn_twobit_unpack")
         return got.value
 
+    # ---- the quality lines run-length packed, and decoded again (gzfastq_mrle) ------------------
+    def mrle_begin(self, max_bytes=0):
+        self._ck(self.L.hpn_mrle_begin(self.h, int(max_bytes)), "hpn_mrle_begin")
+
+    def mrle_add(self, chunk, last=False):
+        """One chunk of FASTQ text into the session's device store; returns the hpn_sort_info."""
+        chunk, n = self._text(chunk)
+        info = _lib.SortInfo()
+        self._ck(self.L.hpn_mrle_add(self.h, _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_mrle_add")
+        return info
+
+    def mrle_finish(self):
+        res = _lib.MrleResult()
+        self._ck(self.L.hpn_mrle_finish(self.h, C.byref(res)), "hpn_mrle_finish")
+        return res
+
+    def mrle_output(self, which, slice_bytes=1 << 24):
+        """One whole output (_lib.MRLE_PACKED / _TEXT / _SHARED), fetched in slices (hpn_mrle_write)."""
+        parts, at = [], 0
+        buf = np.zeros(max(int(slice_bytes), 1), np.uint8)
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_mrle_write(self.h, int(which), at, _ptr(buf), buf.size, C.byref(got)), "hpn_mrle_write")
+            if not got.value:
+                return b"".join(parts)
+            parts.append(buf[:got.value].tobytes())
+            at += got.value
+
     # ---- two files split into pairs and singles (pick_pair) ------------------------------------
     def fastq_pair_begin(self, max_bytes=0):
         self._ck(self.L.hpn_fastq_pair_begin(self.h, int(max_bytes)), "hpn_fastq_pair_begin")

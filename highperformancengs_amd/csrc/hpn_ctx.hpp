@@ -16,6 +16,7 @@ struct hpn_uniqq_state;  // hpn_uniqq.hip
 struct hpn_usort_state;  // hpn_usort.hip
 struct hpn_twobit_state; // hpn_twobit.hip
 struct hpn_pair_state;   // hpn_pair.hip
+struct hpn_mrle_state;   // hpn_mrle.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -101,6 +102,7 @@ struct hpn_ctx {
     hpn_usort_state *us = nullptr;  // hpn_fastq_usort_*: a uniq session of its own, the 64-bit djb2 and the count order
     hpn_twobit_state *tb = nullptr; // hpn_twobit_pack_*: the store, the sizes and offsets, the packed output
     hpn_pair_state *pr = nullptr;   // hpn_fastq_pair_*: a store per mate, the pairing and its certificate, the four outputs
+    hpn_mrle_state *ml = nullptr;   // hpn_mrle_*: the store, the sizes and offsets, the packed, text and shared outputs
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -133,6 +135,7 @@ void uniqq_release(hpn_ctx *c);  // hpn_uniqq.hip
 void usort_release(hpn_ctx *c);  // hpn_usort.hip
 void twobit_release(hpn_ctx *c); // hpn_twobit.hip
 void pair_release(hpn_ctx *c);   // hpn_pair.hip
+void mrle_release(hpn_ctx *c);   // hpn_mrle.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 7
+#define HPN_ABI_VERSION 8
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -560,6 +560,42 @@ int hpn_fastq_pair_begin(hpn_ctx *ctx, uint64_t max_bytes);
 int hpn_fastq_pair_add(hpn_ctx *ctx, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
 int hpn_fastq_pair_finish(hpn_ctx *ctx, hpn_pair_result *result);
 int hpn_fastq_pair_write(hpn_ctx *ctx, int which_output, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
+
+/* ---- gzfastq_mrle.c: the quality lines run-length packed, and decoded again ---------------------------------
+ * gzfastq_mrle frames a stream as readNextNode frames it (see above) and keeps the input's order.  Each quality line is encoded
+ * by a two-pass run-length codec over the six symbols '#' 0, '/' 1, '7' 2, '<' 3, 'B' 4, 'F' 5: pass 1 sums per symbol, over
+ * its maximal runs of length L, L - 2 - (L - 1) / 255; the first output byte has bit s set where that sum is positive; a run of
+ * such a symbol becomes the symbol, (L - 1) / 255 bytes 0xFF and the byte L - 255 * ((L - 1) / 255) - 1, every other run its L
+ * bytes.  An empty line is the flag byte alone; a line encodes to at most its length + 1 bytes.  Any other quality byte indexes
+ * the reference's 8-entry table at 255: there is no answer.  Three outputs:
+ *   HPN_MRLE_PACKED  per record (uint8_t)size and the `size` encoded bytes (the reference's PREFIX_sort_by_seq.fq);
+ *   HPN_MRLE_TEXT    per record what the decoder makes of those encoded bytes and the line's length, and '\n' (its stdout);
+ *   HPN_MRLE_SHARED  what one descriptor receives when the packed file IS standard output (a prefix that begins with '-'): two
+ *                    stdio streams with 4,096-byte buffers, four calls per record -- the line, "\n", the length byte, the
+ *                    encoded bytes; a stream writes its next 4,096 bytes when a non-empty call does not fit into what is left
+ *                    of its buffer; at the end the packed stream's remainder follows and the text's remainder is lost.
+ *
+ *   hpn_mrle_begin   opens a session (closing the context's earlier one).  max_bytes: as for hpn_fastq_uniq_begin.
+ *   hpn_mrle_add     one chunk, the chunk contract of hpn_fastq_sort_add (the same framing, the same info): irregular text --
+ *                    HPN_TEXT_NUL, _LONG_LINE, _PARTIAL, _DENSE -- is reported in info->irregular and closes the session.
+ *                    HPN_E_CAPACITY and HPN_E_DOMAIN (2^31 or more records) as there.
+ *   hpn_mrle_finish  after the last chunk: encodes, decodes and lays out the shared stream on the device, fills *result.  A
+ *                    quality byte outside the six: HPN_E_DOMAIN, result->bad_record is the smallest 0-based ordinal of such a
+ *                    record and the session is closed.
+ *   hpn_mrle_write   copies up to `cap` bytes of output `which` (HPN_MRLE_*; result->out_bytes[which] in all), from byte
+ *                    `offset` on, to `out` (host or device). */
+#define HPN_MRLE_PACKED 0
+#define HPN_MRLE_TEXT 1
+#define HPN_MRLE_SHARED 2
+typedef struct hpn_mrle_result {
+    uint64_t n_records;    /* records encoded */
+    uint64_t out_bytes[3]; /* bytes of the packed, the text and the shared output */
+    int64_t bad_record;    /* -1, or with HPN_E_DOMAIN the smallest ordinal of a record with a quality byte outside #/7<BF */
+} hpn_mrle_result;
+int hpn_mrle_begin(hpn_ctx *ctx, uint64_t max_bytes);
+int hpn_mrle_add(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
+int hpn_mrle_finish(hpn_ctx *ctx, hpn_mrle_result *result);
+int hpn_mrle_write(hpn_ctx *ctx, int which, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
 
 /* ---- ONE text stream framed by several contexts (one per GPU): pieces ----------------------------
  * Record-block sharding of a single FASTQ input (the reference's parallelism stops at
