@@ -103,6 +103,15 @@ class MrleResult(C.Structure):
 MRLE_PACKED, MRLE_TEXT, MRLE_SHARED = 0, 1, 2
 
 
+class RfastqcResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_unique", C.c_uint64), ("hash_clashes", C.c_uint64), ("bad_record", C.c_int64),
+                ("bad_mate", C.c_uint32), ("reason", C.c_uint32)]
+
+
+RFASTQC_DUP, RFASTQC_GC, RFASTQC_QUALITY, RFASTQC_NUCLEOTIDE, RFASTQC_LENGTH = 0, 1, 2, 3, 4
+RFASTQC_BAD_LENGTH, RFASTQC_BAD_QUALITY, RFASTQC_BAD_BYTE, RFASTQC_MATE_SHORT = 1, 2, 3, 4
+
+
 class TextPiece(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("irregular", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -211,6 +220,10 @@ SYMBOLS = [
     ("hpn_mrle_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
     ("hpn_mrle_finish", _int, [_vp, C.POINTER(MrleResult)]),
     ("hpn_mrle_write", _int, [_vp, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_rfastqc_begin", _int, [_vp, _int, _u64, _u32]),
+    ("hpn_rfastqc_add", _int, [_vp, _int, _vp, _u64, _int, C.POINTER(SortInfo)]),
+    ("hpn_rfastqc_finish", _int, [_vp, C.POINTER(RfastqcResult)]),
+    ("hpn_rfastqc_read", _int, [_vp, _int, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_fastq_text_piece_lines", _int, [_vp, _vp, _u64, _u32, _u64, _int, C.POINTER(TextPiece)]),
     ("hpn_fastq_text_piece_count", _int, [_vp, _u64, _u32, C.POINTER(TextInfo)]),
     ("hpn_fastq_text_piece_trim", _int, [_vp, _u64, _i32, _i32, _vp, _u64, C.POINTER(TextInfo)]),
@@ -272,7 +285,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 8:
+    if L.hpn_abi_version() != 9:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -444,6 +444,47 @@ class Context:
             parts.append(buf[:got.value].tobytes())
             at += got.value
 
+    # ---- Rfastqc.R's qsort_hash_count from FASTQ text (rfastqc_tally) ----------------------------
+    def rfastqc_begin(self, paired=False, max_bytes=0, hash_bits=0):
+        self._ck(self.L.hpn_rfastqc_begin(self.h, int(bool(paired)), int(max_bytes), int(hash_bits)), "hpn_rfastqc_begin")
+
+    def rfastqc_add(self, mate, chunk, last=False):
+        """One chunk of mate 0 or 1 into that mate's device store; returns the hpn_sort_info."""
+        chunk, n = self._text(chunk)
+        info = _lib.SortInfo()
+        self._ck(self.L.hpn_rfastqc_add(self.h, int(mate), _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_rfastqc_add")
+        return info
+
+    def rfastqc_finish(self):
+        res = _lib.RfastqcResult()
+        self._ck(self.L.hpn_rfastqc_finish(self.h, C.byref(res)), "hpn_rfastqc_finish")
+        return res
+
+    def rfastqc_array(self, which, mate=0, slice_elems=1 << 22):
+        """One whole array (_lib.RFASTQC_*) of a finished session as numpy, fetched in slices (hpn_rfastqc_read)."""
+        buf = np.zeros(max(int(slice_elems), 1), np.float64 if which == _lib.RFASTQC_GC else np.int32)
+        parts, at = [], 0
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_rfastqc_read(self.h, int(which), int(mate), at, _ptr(buf), buf.size, C.byref(got)), "hpn_rfastqc_read")
+            if not got.value:
+                return np.concatenate(parts) if parts else buf[:0].copy()
+            parts.append(buf[:got.value].copy())
+            at += got.value
+
+    def rfastqc(self, fq1, fq2=None, hash_bits=0):
+        """qsort_hash_count(fq1, fq2) over FASTQ text held in memory: (result, list) with the list's 5 (9) elements as numpy arrays --
+        the duplicate counts, then gc, quality, nucleotide, length of mate 1 (and of mate 2)."""
+        self.rfastqc_begin(fq2 is not None, hash_bits=hash_bits)
+        self.rfastqc_add(0, fq1, last=True)
+        if fq2 is not None:
+            self.rfastqc_add(1, fq2, last=True)
+        res = self.rfastqc_finish()
+        out = [self.rfastqc_array(_lib.RFASTQC_DUP)]
+        for mate in range(2 if fq2 is not None else 1):
+            out += [self.rfastqc_array(w, mate) for w in (_lib.RFASTQC_GC, _lib.RFASTQC_QUALITY, _lib.RFASTQC_NUCLEOTIDE, _lib.RFASTQC_LENGTH)]
+        return res, out
+
     # ---- two files split into pairs and singles (pick_pair) ------------------------------------
     def fastq_pair_begin(self, max_bytes=0):
         self._ck(self.L.hpn_fastq_pair_begin(self.h, int(max_bytes)), "hpn_fastq_pair_begin")

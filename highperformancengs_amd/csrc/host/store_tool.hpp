@@ -1,5 +1,5 @@
 // store_tool.hpp -- what the tools over a store session share (gzfastq_uniq, gzfastq_uniqQ, gzfastq_uniq_sort, gzfastq_sort,
-// fastq2twobit, pick_pair, gzfastq_mrle): the refusal, the outcome of an *_add call, a file or a stream in memory into the session, the host's
+// fastq2twobit, pick_pair, gzfastq_mrle, rfastqc_tally): the refusal, the outcome of an *_add call, a file or a stream in memory into the session, the host's
 // framing of text the device refused, and a device output through GzWriter.  A tool hands in its `add`: a callable
 // bool(const void *text, uint64_t n, bool last) around its family's *_add, false when the chunk was not regular.
 #pragma once

@@ -17,6 +17,7 @@ struct hpn_usort_state;  // hpn_usort.hip
 struct hpn_twobit_state; // hpn_twobit.hip
 struct hpn_pair_state;   // hpn_pair.hip
 struct hpn_mrle_state;   // hpn_mrle.hip
+struct hpn_rfastqc_state; // hpn_rqcfile.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -103,6 +104,7 @@ struct hpn_ctx {
     hpn_twobit_state *tb = nullptr; // hpn_twobit_pack_*: the store, the sizes and offsets, the packed output
     hpn_pair_state *pr = nullptr;   // hpn_fastq_pair_*: a store per mate, the pairing and its certificate, the four outputs
     hpn_mrle_state *ml = nullptr;   // hpn_mrle_*: the store, the sizes and offsets, the packed, text and shared outputs
+    hpn_rfastqc_state *rq = nullptr; // hpn_rfastqc_*: a store per mate, the grouping's arrays, the list's elements
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -136,6 +138,7 @@ void usort_release(hpn_ctx *c);  // hpn_usort.hip
 void twobit_release(hpn_ctx *c); // hpn_twobit.hip
 void pair_release(hpn_ctx *c);   // hpn_pair.hip
 void mrle_release(hpn_ctx *c);   // hpn_mrle.hip
+void rfastqc_release(hpn_ctx *c); // hpn_rqcfile.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

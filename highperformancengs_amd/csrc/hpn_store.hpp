@@ -1,5 +1,5 @@
-// hpn_store.hpp -- the device store behind the seven store-backed entry points (hpn_fastq_uniq_*, _uniqq_*, _usort_*, _sort_*, _pair_*,
-// hpn_twobit_pack_*, hpn_mrle_*) and the session around it.  The store: a stream's bytes are appended as they come and framed WHERE THEY
+// hpn_store.hpp -- the device store behind the eight store-backed entry points (hpn_fastq_uniq_*, _uniqq_*, _usort_*, _sort_*, _pair_*,
+// hpn_twobit_pack_*, hpn_mrle_*, hpn_rfastqc_*) and the session around it.  The store: a stream's bytes are appended as they come and framed WHERE THEY
 // LIE (no carry is copied: the next chunk's framing starts at the first unfinished record), one descriptor per record.  What a
 // descriptor holds is the caller's: it hands in the kernel that writes them (kernels/fastq_uniq.hip: k_uniq_keys,
 // kernels/fastq_sort.hip: k_sort_frame) behind the line index of kernels/fastq_text.hip.  The session: one or two stores under

@@ -1,4 +1,4 @@
-// sort_desc.hpp -- the record descriptor of the device store behind hpn_fastq_sort_*, hpn_twobit_pack_*, hpn_fastq_pair_* and hpn_mrle_*
+// sort_desc.hpp -- the record descriptor of the device store behind hpn_fastq_sort_*, hpn_twobit_pack_*, hpn_fastq_pair_*, hpn_mrle_* and hpn_rfastqc_*
 // (written by k_sort_frame, kernels/fastq_sort.hip).  Plain C++: the kernels and the host (hpn_sort.hip, hpn_twobit.hip,
 // hpn_pair.hip) read the same struct.
 #pragma once

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 8
+#define HPN_ABI_VERSION 9
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -140,7 +140,8 @@ int hpn_fastq_tally_devptr(hpn_ctx *ctx, uint64_t **d_acc);
  *   gc[i]                      = #{'G','C'} / len of read i, as double       double[n]
  * Adds into quality / nucleotide / length (the plugin callocs them, :37-40) and writes
  * gc.  Any of the four pointers may be NULL.  The duplicate-count vector (list element
- * 1: hash of the first 50 bases, qsort) is the dedup family and is not produced here.
+ * 1) and a path from a file are hpn_rfastqc_* below; this entry point takes arrays the caller
+ * has framed.
  * Domain (else HPN_E_DOMAIN): 1 <= len <= 300 (MaxLen; the plugin writes out of bounds
  * otherwise), quality byte < 128. */
 #define HPN_RQC_MAXLEN 300
@@ -596,6 +597,63 @@ int hpn_mrle_begin(hpn_ctx *ctx, uint64_t max_bytes);
 int hpn_mrle_add(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
 int hpn_mrle_finish(hpn_ctx *ctx, hpn_mrle_result *result);
 int hpn_mrle_write(hpn_ctx *ctx, int which, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
+
+/* ---- Rfastqc.R's one call: qsort_hash_count(fq1, fq2) of Rgzfastq_uniq.c, from FASTQ text ----------------------
+ * The whole list the plugin returns -- 5 elements single-end, 9 paired -- from one or two streams framed as readNextNode frames
+ * them (see hpn_fastq_sort_*).  With L1, L2 the sequence lengths of a record (a pair, ordinal by ordinal):
+ *
+ *   HPN_RFASTQC_DUP         int32[n_unique]   the count of every distinct KEY, descending (element 1).  The key is the C string the
+ *                                             plugin assembles in a zeroed 512-byte buffer:
+ *                                               single-end               s1[0:50] if L1 > 75, else s1
+ *                                               L2 > 75,  L1 < 50        s1                   (a NUL gap cuts mate 2 off)
+ *                                               L2 > 75,  L1 >= 50       s1[0:50] + s2[0:50]  (mate 2 overwrites s1[50:])
+ *                                               L2 <= 75, L1 > 75        s1[0:50]             (mate 2 lies behind a NUL gap)
+ *                                               L2 <= 75, L1 <= 75       s1 + s2              (no separator: AC/GT is ACG/T)
+ *                                             compared bytewise.  Only the multiset of counts is defined (table and qsort order
+ *                                             cannot be seen in it).
+ *   HPN_RFASTQC_GC          double[n_records] #{'G','C'} / L per read of `mate` (elements 2, 6)
+ *   HPN_RFASTQC_QUALITY     int32[128*300]    quality[q + 128*pos], over the QUALITY line's own length (elements 3, 7)
+ *   HPN_RFASTQC_NUCLEOTIDE  int32[5*300]      nucleotide[5*pos + code], codes as for hpn_fastq_rqc (elements 4, 8)
+ *   HPN_RFASTQC_LENGTH      int32[300]        length[L - 1] (elements 5, 9)
+ *
+ *   hpn_rfastqc_begin   opens a session (closing the context's earlier one).  paired, max_bytes, hash_bits: as for
+ *                       hpn_fastq_uniq_begin (hash_bits 0: 64 bits; a small value makes clashes the rule, for tests -- the answer
+ *                       never rests on the hash).
+ *   hpn_rfastqc_add     one chunk of `mate` (0, or 1 in a paired session), the chunk contract and the info of hpn_fastq_sort_add;
+ *                       the mates' streams may be fed in any interleaving.  Irregular text closes the session.  HPN_E_CAPACITY
+ *                       and HPN_E_DOMAIN (2^31 or more records: the plugin's cells are int) as there.
+ *   hpn_rfastqc_finish  after every mate's last chunk: tallies and groups on the device, fills *result.  Records of mate 2 behind
+ *                       mate 1's last are ignored, as the plugin never reads them.  Where the plugin has no answer it returns
+ *                       HPN_E_DOMAIN, names the first offending record and mate (in the plugin's order: per record mate 1, then
+ *                       mate 2) with the reason, and closes the session with nothing to read:
+ *                         HPN_RFASTQC_BAD_LENGTH   L outside 1..300 (it writes outside Length[] / the matrices)
+ *                         HPN_RFASTQC_BAD_QUALITY  a quality line longer than 300
+ *                         HPN_RFASTQC_BAD_BYTE     a sequence or quality byte >= 128 (a negative index through char)
+ *                         HPN_RFASTQC_MATE_SHORT   mate 2 has fewer records than mate 1 (it dereferences NULL); bad_record is
+ *                                                  mate 2's record count, bad_mate 1
+ *   hpn_rfastqc_read    copies up to cap_elems ELEMENTS of array `which` of `mate` (mate is ignored for HPN_RFASTQC_DUP), from
+ *                       element first_elem on, to `out` (host or device); *got: how many.  Call until *got is 0. */
+#define HPN_RFASTQC_DUP 0
+#define HPN_RFASTQC_GC 1
+#define HPN_RFASTQC_QUALITY 2
+#define HPN_RFASTQC_NUCLEOTIDE 3
+#define HPN_RFASTQC_LENGTH 4
+#define HPN_RFASTQC_BAD_LENGTH 1u
+#define HPN_RFASTQC_BAD_QUALITY 2u
+#define HPN_RFASTQC_BAD_BYTE 3u
+#define HPN_RFASTQC_MATE_SHORT 4u
+typedef struct hpn_rfastqc_result {
+    uint64_t n_records;    /* records (pairs) tallied */
+    uint64_t n_unique;     /* distinct keys: the length of HPN_RFASTQC_DUP */
+    uint64_t hash_clashes; /* sorted neighbours with equal grouping hashes over different keys */
+    int64_t bad_record;    /* -1, or with HPN_E_DOMAIN the 0-based ordinal of the first record the plugin has no answer for */
+    uint32_t bad_mate;     /* ... and its mate (0, 1) */
+    uint32_t reason;       /* 0, or HPN_RFASTQC_BAD_* / _MATE_SHORT */
+} hpn_rfastqc_result;
+int hpn_rfastqc_begin(hpn_ctx *ctx, int paired, uint64_t max_bytes, uint32_t hash_bits);
+int hpn_rfastqc_add(hpn_ctx *ctx, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
+int hpn_rfastqc_finish(hpn_ctx *ctx, hpn_rfastqc_result *result);
+int hpn_rfastqc_read(hpn_ctx *ctx, int which, int mate, uint64_t first_elem, void *out, uint64_t cap_elems, uint64_t *got);
 
 /* ---- ONE text stream framed by several contexts (one per GPU): pieces ----------------------------
  * Record-block sharding of a single FASTQ input (the reference's parallelism stops at
