@@ -135,6 +135,21 @@ class RawInfo(C.Structure):
                 ("tail_bytes", C.c_uint32)]
 
 
+class SplitInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_blocks", C.c_uint64), ("payload_bytes", C.c_uint64), ("stored_bytes", C.c_uint64),
+                ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32), ("tid_first", C.c_int32), ("tid_last", C.c_int32),
+                ("reason", C.c_uint32), ("open_bytes", C.c_uint32)]
+
+
+class SplitBlock(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("crc", C.c_uint32), ("tid", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class SplitResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_blocks", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
+                ("reason", C.c_uint32), ("n_ref", C.c_uint32)]
+
+
 class GzInfo(C.Structure):
     _fields_ = [("n_bytes", C.c_uint64), ("end_bit", C.c_uint64), ("status", C.c_uint32), ("bad_chunk", C.c_uint32),
                 ("final_chunk", C.c_uint32), ("reserved", C.c_uint32)]
@@ -239,6 +254,13 @@ SYMBOLS = [
     ("hpn_bam_raw_index_dev", _int, [_vp, _vp, _vp, _u64, _u32, _vp, C.POINTER(RawInfo)]),
     ("hpn_depth_add_raw_dev", _int, [_vp, _vp]),
     ("hpn_window_add_raw_dev", _int, [_vp, _vp]),
+    ("hpn_bgzf_stored_dev", _int, [_vp, _vp, _vp, _u32, _vp]),
+    ("hpn_bam_split_begin", _int, [_vp, _i32, _int]),
+    ("hpn_bam_split_add_raw_dev", _int, [_vp, _vp, _int, C.POINTER(SplitInfo)]),
+    ("hpn_bam_split_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_bam_split_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_split_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_split_finish", _int, [_vp, C.POINTER(SplitResult), _vp]),
     ("hpn_depth_begin", _int, [_vp, _i32, _u32, _u32]),
     ("hpn_depth_begin_w", _int, [_vp, _i32, _u32, _u32, _u32]),
     ("hpn_depth_progress", _int, [_vp, C.POINTER(_u64)]),
@@ -285,7 +307,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 9:
+    if L.hpn_abi_version() != 10:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -679,6 +679,53 @@ class Context:
                  "hpn_window_finish")
         return bins, gc, ln, touched, nc.value
 
+    # ---- bamSplitChr: target boundaries, domain checks, BGZF cuts (hpn_bam_split_*) ----
+    def split_begin(self, n_ref, level0=False):
+        self._ck(self.L.hpn_bam_split_begin(self.h, n_ref, 1 if level0 else 0), "hpn_bam_split_begin")
+
+    def split_add_raw_dev(self, d_raw, last=False):
+        """The batch hpn_bam_raw_index_dev indexed last (d_raw None: no records, only `last`) -> SplitInfo."""
+        info = _lib.SplitInfo()
+        self._ck(self.L.hpn_bam_split_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, 1 if last else 0, C.byref(info)),
+                 "hpn_bam_split_add_raw_dev")
+        return info
+
+    def split_blocks(self, n):
+        """The n closed blocks of the last split_add_raw_dev -> ctypes array of SplitBlock (off, len, crc, tid)."""
+        out = (_lib.SplitBlock * max(int(n), 1))()
+        got = C.c_uint64(0)
+        self._ck(self.L.hpn_bam_split_blocks(self.h, 0, out, int(n), C.byref(got)), "hpn_bam_split_blocks")
+        return out[:got.value]
+
+    def _split_bytes(self, fn, name):
+        p, n = C.c_void_p(0), C.c_uint64(0)
+        self._ck(fn(self.h, C.byref(p), C.byref(n)), name)
+        host = np.zeros(n.value, np.uint8)
+        if n.value:
+            self._ck(self.L.hpn_memcpy_d2h(self.h, _ptr(host), p, n.value), "hpn_memcpy_d2h")
+            self.sync()
+        return host.tobytes()
+
+    def split_payload(self):
+        """The payload buffer of the last call up to the end of its last closed block, copied to the host."""
+        return self._split_bytes(self.L.hpn_bam_split_payload_dev, "hpn_bam_split_payload_dev")
+
+    def split_stored(self):
+        """The closed blocks of the last call as the device framed them (level 0), copied to the host."""
+        return self._split_bytes(self.L.hpn_bam_split_stored_dev, "hpn_bam_split_stored_dev")
+
+    def bgzf_stored_dev(self, d_data, spans, d_image):
+        """spans: (off, img_off, len, crc) per block -> each framed as a stored BGZF block of len + 31 bytes at d_image + img_off."""
+        arr = np.zeros(len(spans), np.dtype([("off", "<u8"), ("img_off", "<u8"), ("len", "<u4"), ("crc", "<u4")]))
+        for k, sp in enumerate(spans):
+            arr[k] = sp
+        self._ck(self.L.hpn_bgzf_stored_dev(self.h, _ptr(d_data), _ptr(arr) if len(spans) else None, len(spans), _ptr(d_image)), "hpn_bgzf_stored_dev")
+
+    def split_finish(self, n_ref):
+        res, counts = _lib.SplitResult(), np.zeros(max(n_ref, 1), np.uint64)
+        self._ck(self.L.hpn_bam_split_finish(self.h, C.byref(res), _ptr(counts)), "hpn_bam_split_finish")
+        return res, counts[:n_ref]
+
     # ---- collectives / synthetic -----------------------------------------
     def comm_init(self, rank, n_ranks, unique_id: bytes):
         buf = (C.c_uint8 * _lib.UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

@@ -104,6 +104,7 @@ int hpn_ctx_destroy(hpn_ctx *c)
     pair_release(c);
     mrle_release(c);
     rfastqc_release(c);
+    split_release(c);
     if (c->d_acc) (void)hipFree(c->d_acc);
     if (c->h_acc) (void)hipHostFree(c->h_acc);
     if (c->t_state) (void)hipFree(c->t_state);

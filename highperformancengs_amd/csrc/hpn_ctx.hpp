@@ -18,6 +18,7 @@ struct hpn_twobit_state; // hpn_twobit.hip
 struct hpn_pair_state;   // hpn_pair.hip
 struct hpn_mrle_state;   // hpn_mrle.hip
 struct hpn_rfastqc_state; // hpn_rqcfile.hip
+struct hpn_split_state;  // hpn_split.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -105,6 +106,7 @@ struct hpn_ctx {
     hpn_pair_state *pr = nullptr;   // hpn_fastq_pair_*: a store per mate, the pairing and its certificate, the four outputs
     hpn_mrle_state *ml = nullptr;   // hpn_mrle_*: the store, the sizes and offsets, the packed, text and shared outputs
     hpn_rfastqc_state *rq = nullptr; // hpn_rfastqc_*: a store per mate, the grouping's arrays, the list's elements
+    hpn_split_state *sp = nullptr;   // hpn_bam_split_*: keys, cuts and block list of the batch, the payload, the open block
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -139,6 +141,7 @@ void twobit_release(hpn_ctx *c); // hpn_twobit.hip
 void pair_release(hpn_ctx *c);   // hpn_pair.hip
 void mrle_release(hpn_ctx *c);   // hpn_mrle.hip
 void rfastqc_release(hpn_ctx *c); // hpn_rqcfile.hip
+void split_release(hpn_ctx *c);  // hpn_split.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

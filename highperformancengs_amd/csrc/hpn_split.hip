@@ -1,0 +1,267 @@
+// hpn_split.hip -- C ABI of bamSplitChr.c: hpn_bam_split_begin / _add_raw_dev / _blocks / _payload_dev / _stored_dev / _finish.
+// Kernels: kernels/bam_split.hip; the CRC-32 of the closed blocks through hpn_crc32_dev (kernels/crc32.hip).
+//
+// The session sees the batches hpn_bam_raw_index_dev has indexed, in file order.  Per batch: keys and checks, the batch's
+// records copied behind the bytes of the block the batch before left open (the payload buffer), the cuts, the block list, the
+// CRCs, for level 0 the stored image; the last block stays open unless it is full, its target has ended or the file has.
+#include <string.h>
+
+#include <vector>
+
+#include "hpn_ctx.hpp"
+
+namespace hpn {
+// kernels/bam_split.hip
+hipError_t launch_split_keys(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, int32_t n_ref, uint64_t base, uint32_t fill,
+                             uint32_t open_key, const void *prev, void *next, u64 *Q, uint32_t *key, u64 *counts, u64 *info, hipStream_t st);
+uint32_t split_tiles(uint64_t m);
+hipError_t launch_split_cuts(const u64 *Q, const uint32_t *key, uint64_t m, int32_t n_ref, uint32_t *a, uint32_t *b, uint32_t *c, uint32_t *mark,
+                             u64 *tile_sum, u64 *info, hipStream_t st);
+hipError_t launch_split_emit(const u64 *Q, const uint32_t *key, const uint32_t *next, const uint32_t *mark, uint64_t m, int32_t n_ref,
+                             const u64 *tile_base, void *out, uint64_t n_out, hipStream_t st);
+hipError_t launch_split_stored(const uint8_t *pay, const void *specs, uint32_t n, uint8_t *img, hipStream_t st);
+}  // namespace hpn
+
+using namespace hpn;
+
+namespace {
+constexpr uint32_t kFull = 0xff00;
+constexpr uint32_t kNoKey = 0xfffffffeu;
+typedef hpn_stored_span StoredSpec;      // (kernels/bam_split.hip reads the same layout)
+}  // namespace
+
+struct hpn_split_state {
+    bool open = false, dead = false, ended = false;
+    int32_t n_ref = 0;
+    bool level0 = false;
+    Scratch Q, key, ja, jb, jc, mark, tiles, blocks, pay, img, keep, specs, counts, state, info;
+    int turn = 0;                    // which of the two carried states the next batch reads
+    uint64_t records = 0, n_blocks = 0;
+    uint32_t fill = 0;               // bytes of the open block (in `keep`)
+    int32_t open_tid = -1;
+    int64_t bad_record = -1;
+    int32_t bad_tid = 0, bad_pos = 0;
+    uint32_t reason = 0;
+    std::vector<hpn_split_block> list;   // the closed blocks of the last call
+    uint64_t payload_bytes = 0, stored_bytes = 0;
+};
+
+namespace hpn {
+void split_release(hpn_ctx *c)
+{
+    hpn_split_state *u = c->sp;
+    if (!u) return;
+    Scratch *ss[] = {&u->Q, &u->key, &u->ja, &u->jb, &u->jc, &u->mark, &u->tiles, &u->blocks, &u->pay, &u->img, &u->keep, &u->specs, &u->counts,
+                     &u->state, &u->info};
+    for (Scratch *s : ss)
+        if (s->p) (void)hipFree(s->p);
+    delete u;
+    c->sp = nullptr;
+}
+}  // namespace hpn
+
+extern "C" {
+
+int hpn_bam_split_begin(hpn_ctx *c, int32_t n_ref, int level0)
+{
+    if (!c || n_ref < 0) return HPN_E_ARG;
+    HPN_HIP(c, hipSetDevice(c->device));
+    if (!c->sp) c->sp = new hpn_split_state;
+    hpn_split_state *u = c->sp;
+    int rc;
+    if ((rc = scratch_reserve(c, u->counts, ((size_t)n_ref + 1) * sizeof(u64))) != HPN_OK) return rc;
+    if ((rc = scratch_reserve(c, u->state, 64)) != HPN_OK || (rc = scratch_reserve(c, u->info, 64)) != HPN_OK) return rc;
+    if ((rc = scratch_reserve(c, u->keep, kFull + 64)) != HPN_OK) return rc;
+    HPN_HIP(c, hipMemsetAsync(u->counts.p, 0, ((size_t)n_ref + 1) * sizeof(u64), c->stream));
+    HPN_HIP(c, hipMemsetAsync(u->state.p, 0, 64, c->stream));
+    u->open = true, u->dead = false, u->ended = false;
+    u->n_ref = n_ref, u->level0 = level0 != 0;
+    u->turn = 0, u->records = 0, u->n_blocks = 0, u->fill = 0, u->open_tid = -1;
+    u->bad_record = -1, u->bad_tid = 0, u->bad_pos = 0, u->reason = 0;
+    u->list.clear(), u->payload_bytes = 0, u->stored_bytes = 0;
+    return HPN_OK;
+}
+
+static void split_report(const hpn_split_state *u, hpn_split_info *info)
+{
+    info->bad_record = u->bad_record, info->bad_tid = u->bad_tid, info->bad_pos = u->bad_pos, info->reason = u->reason;
+    info->tid_first = 0, info->tid_last = -1;
+}
+
+int hpn_bam_split_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, int last, hpn_split_info *info)
+{
+    if (!c || !info) return HPN_E_ARG;
+    hpn_split_state *u = c->sp;
+    if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_add_raw_dev before hpn_bam_split_begin");
+    if (u->ended) return fail(c, HPN_E_STATE, "hpn_bam_split_add_raw_dev behind the call that ended the file");
+    HPN_HIP(c, hipSetDevice(c->device));
+    memset(info, 0, sizeof *info);
+    u->list.clear(), u->payload_bytes = 0, u->stored_bytes = 0;
+    const uint64_t n = d_raw ? c->r_n : 0;
+    info->n_records = n;
+    split_report(u, info);
+    if (u->dead) return HPN_OK;                        // outside the domain: nothing more is made
+    if (n > 0xfffffff0ull) return fail(c, HPN_E_ARG, "more than 2^32 records in one batch");
+    const uint64_t m = n + 1;
+    int rc;
+    if ((rc = scratch_reserve(c, u->Q, (m + 1) * sizeof(u64))) != HPN_OK || (rc = scratch_reserve(c, u->key, (m + 1) * sizeof(uint32_t))) != HPN_OK ||
+        (rc = scratch_reserve(c, u->ja, (m + 1) * sizeof(uint32_t))) != HPN_OK || (rc = scratch_reserve(c, u->jb, (m + 1) * sizeof(uint32_t))) != HPN_OK ||
+        (rc = scratch_reserve(c, u->jc, (m + 1) * sizeof(uint32_t))) != HPN_OK || (rc = scratch_reserve(c, u->mark, (m + 1) * sizeof(uint32_t))) != HPN_OK ||
+        (rc = scratch_reserve(c, u->tiles, ((size_t)split_tiles(m) + 1) * sizeof(u64))) != HPN_OK)
+        return rc;
+    const u64 init[4] = {~0ull, 0, 0, 0};
+    HPN_HIP(c, hipMemcpyAsync(u->info.p, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    uint8_t *states = (uint8_t *)u->state.p;
+    HPN_HIP(c, launch_split_keys(d_raw, (const uint64_t *)c->r_off.p, n, u->n_ref, u->records, u->fill, u->fill ? (uint32_t)u->open_tid : kNoKey,
+                                 states + 16 * u->turn, states + 16 * (u->turn ^ 1), (u64 *)u->Q.p, (uint32_t *)u->key.p, (u64 *)u->counts.p,
+                                 (u64 *)u->info.p, c->stream));
+    u64 h[4];
+    HPN_HIP(c, hipMemcpyAsync(h, u->info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HPN_HIP(c, hipStreamSynchronize(c->stream));       // (also: `init` is the caller's stack)
+    u->turn ^= 1;
+    if (h[0] != ~0ull) {                               // the first record outside the domain: refID and pos for the message
+        const uint64_t ord = h[0] >> 3;
+        uint64_t off = 0;
+        int32_t f[2] = {0, 0};
+        HPN_HIP(c, hipMemcpyAsync(&off, (const uint64_t *)c->r_off.p + (ord - u->records), sizeof off, hipMemcpyDeviceToHost, c->stream));
+        HPN_HIP(c, hipStreamSynchronize(c->stream));
+        HPN_HIP(c, hipMemcpyAsync(f, d_raw + off + 4, sizeof f, hipMemcpyDeviceToHost, c->stream));
+        HPN_HIP(c, hipStreamSynchronize(c->stream));
+        u->dead = true;
+        u->bad_record = (int64_t)ord, u->bad_tid = f[0], u->bad_pos = f[1], u->reason = (uint32_t)(h[0] & 7);
+        u->records += n;
+        split_report(u, info);
+        return HPN_OK;
+    }
+    u->records += n;
+    // the payload: the open block's bytes, then the batch's records as they lie in the stream
+    const uint64_t rec_bytes = n ? h[2] - h[1] : 0, total = u->fill + rec_bytes;
+    if ((rc = scratch_reserve(c, u->pay, total + 64)) != HPN_OK) return rc;
+    if (u->fill) HPN_HIP(c, hipMemcpyAsync(u->pay.p, u->keep.p, u->fill, hipMemcpyDeviceToDevice, c->stream));
+    if (rec_bytes) HPN_HIP(c, hipMemcpyAsync((uint8_t *)u->pay.p + u->fill, d_raw + h[1], rec_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HPN_HIP(c, launch_split_cuts((const u64 *)u->Q.p, (const uint32_t *)u->key.p, m, u->n_ref, (uint32_t *)u->ja.p, (uint32_t *)u->jb.p,
+                                 (uint32_t *)u->jc.p, (uint32_t *)u->mark.p, (u64 *)u->tiles.p, (u64 *)u->info.p, c->stream));
+    u64 nb = 0;
+    HPN_HIP(c, hipMemcpyAsync(&nb, (const u64 *)u->info.p + 3, sizeof nb, hipMemcpyDeviceToHost, c->stream));
+    HPN_HIP(c, hipStreamSynchronize(c->stream));
+    if (nb > total / 32 + 2) return fail(c, HPN_E_HIP, "hpn_bam_split: %llu blocks out of %llu bytes", (unsigned long long)nb, (unsigned long long)total);
+    u->list.resize(nb);
+    if (nb) {
+        if ((rc = scratch_reserve(c, u->blocks, nb * sizeof(hpn_split_block))) != HPN_OK) return rc;
+        HPN_HIP(c, launch_split_emit((const u64 *)u->Q.p, (const uint32_t *)u->key.p, (const uint32_t *)u->ja.p, (const uint32_t *)u->mark.p, m,
+                                     u->n_ref, (const u64 *)u->tiles.p, u->blocks.p, nb, c->stream));
+        HPN_HIP(c, hipMemcpyAsync(u->list.data(), u->blocks.p, nb * sizeof(hpn_split_block), hipMemcpyDeviceToHost, c->stream));
+        HPN_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    for (const hpn_split_block &b : u->list)          // (what the host copies by must lie inside the payload)
+        if (b.len == 0 || b.len > kFull || b.off > total || b.len > total - b.off)
+            return fail(c, HPN_E_HIP, "hpn_bam_split: a block of %u bytes at %llu of %llu", b.len, (unsigned long long)b.off, (unsigned long long)total);
+    // the last block stays open while its target may go on
+    u->fill = 0, u->open_tid = -1;
+    if (!last && nb) {
+        const hpn_split_block &b = u->list.back();
+        if (b.off + b.len == total && b.len < kFull) {
+            HPN_HIP(c, hipMemcpyAsync(u->keep.p, (const uint8_t *)u->pay.p + b.off, b.len, hipMemcpyDeviceToDevice, c->stream));
+            u->fill = b.len, u->open_tid = b.tid;
+            u->list.pop_back();
+        }
+    }
+    if (last) u->ended = true;
+    const size_t nc = u->list.size();
+    if (nc) {
+        std::vector<hpn_span> spans(nc);
+        std::vector<uint32_t> crcs(nc);
+        for (size_t k = 0; k < nc; ++k) spans[k] = hpn_span{u->list[k].off, u->list[k].len};
+        if ((rc = hpn_crc32_dev(c, (const uint8_t *)u->pay.p, spans.data(), (uint32_t)nc, crcs.data())) != HPN_OK) return rc;
+        for (size_t k = 0; k < nc; ++k) u->list[k].crc = crcs[k];
+        u->payload_bytes = u->list.back().off + u->list.back().len;
+        if (u->level0) {
+            std::vector<StoredSpec> specs(nc);
+            uint64_t at = 0;
+            for (size_t k = 0; k < nc; ++k) {
+                specs[k] = StoredSpec{u->list[k].off, at, u->list[k].len, u->list[k].crc};
+                at += (uint64_t)u->list[k].len + 31;
+            }
+            if ((rc = scratch_reserve(c, u->specs, nc * sizeof(StoredSpec))) != HPN_OK || (rc = scratch_reserve(c, u->img, at + 64)) != HPN_OK) return rc;
+            HPN_HIP(c, hipMemcpyAsync(u->specs.p, specs.data(), nc * sizeof(StoredSpec), hipMemcpyHostToDevice, c->stream));
+            HPN_HIP(c, launch_split_stored((const uint8_t *)u->pay.p, u->specs.p, (uint32_t)nc, (uint8_t *)u->img.p, c->stream));
+            u->stored_bytes = at;
+        }
+        info->tid_first = u->list.front().tid, info->tid_last = u->list.back().tid;
+    }
+    HPN_HIP(c, hipStreamSynchronize(c->stream));
+    u->n_blocks += nc;
+    info->n_blocks = nc, info->payload_bytes = u->payload_bytes, info->stored_bytes = u->stored_bytes, info->open_bytes = u->fill;
+    return HPN_OK;
+}
+
+int hpn_bgzf_stored_dev(hpn_ctx *c, const uint8_t *d_data, const hpn_stored_span *spans, uint32_t n_spans, uint8_t *d_image)
+{
+    if (!c || (n_spans && (!d_data || !spans || !d_image))) return HPN_E_ARG;
+    for (uint32_t k = 0; k < n_spans; ++k)
+        if (spans[k].len == 0 || spans[k].len > kFull) return fail(c, HPN_E_ARG, "hpn_bgzf_stored_dev: span %u has %u bytes", k, spans[k].len);
+    if (!n_spans) return HPN_OK;
+    HPN_HIP(c, hipSetDevice(c->device));
+    if (!c->sp) c->sp = new hpn_split_state;
+    hpn_split_state *u = c->sp;
+    const int rc = scratch_reserve(c, u->specs, (size_t)n_spans * sizeof(StoredSpec));
+    if (rc != HPN_OK) return rc;
+    HPN_HIP(c, hipMemcpyAsync(u->specs.p, spans, (size_t)n_spans * sizeof(StoredSpec), hipMemcpyHostToDevice, c->stream));
+    HPN_HIP(c, launch_split_stored(d_data, u->specs.p, n_spans, d_image, c->stream));
+    HPN_HIP(c, hipStreamSynchronize(c->stream));
+    return HPN_OK;
+}
+
+int hpn_bam_split_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
+{
+    if (!c || !n) return HPN_E_ARG;
+    hpn_split_state *u = c->sp;
+    if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_blocks before hpn_bam_split_begin");
+    const uint64_t have = u->list.size();
+    if (first > have) return fail(c, HPN_E_ARG, "block %llu of %llu", (unsigned long long)first, (unsigned long long)have);
+    *n = have - first;
+    if (*n > cap) return HPN_E_CAPACITY;
+    if (*n && !out) return HPN_E_ARG;
+    if (*n) memcpy(out, u->list.data() + first, (size_t)*n * sizeof(hpn_split_block));
+    return HPN_OK;
+}
+
+int hpn_bam_split_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n_bytes)
+{
+    if (!c || !d_payload || !n_bytes) return HPN_E_ARG;
+    hpn_split_state *u = c->sp;
+    if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_payload_dev before hpn_bam_split_begin");
+    *d_payload = (const uint8_t *)u->pay.p, *n_bytes = u->payload_bytes;
+    return HPN_OK;
+}
+
+int hpn_bam_split_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_bytes)
+{
+    if (!c || !d_image || !n_bytes) return HPN_E_ARG;
+    hpn_split_state *u = c->sp;
+    if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_stored_dev before hpn_bam_split_begin");
+    if (!u->level0) return fail(c, HPN_E_STATE, "hpn_bam_split_stored_dev: the session was not begun with level0");
+    *d_image = (const uint8_t *)u->img.p, *n_bytes = u->stored_bytes;
+    return HPN_OK;
+}
+
+int hpn_bam_split_finish(hpn_ctx *c, hpn_split_result *res, uint64_t *counts)
+{
+    if (!c || !res) return HPN_E_ARG;
+    hpn_split_state *u = c->sp;
+    if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_finish before hpn_bam_split_begin");
+    if (!u->dead && u->fill) return fail(c, HPN_E_STATE, "hpn_bam_split_finish with a block open: the last hpn_bam_split_add_raw_dev takes last = 1");
+    HPN_HIP(c, hipSetDevice(c->device));
+    memset(res, 0, sizeof *res);
+    res->n_records = u->records, res->n_blocks = u->n_blocks, res->n_ref = (uint32_t)u->n_ref;
+    res->bad_record = u->bad_record, res->bad_tid = u->bad_tid, res->bad_pos = u->bad_pos, res->reason = u->reason;
+    if (counts && u->n_ref) {
+        // (per batch the counts moved by ordinals INSIDE the batch: every batch adds its own records, the sums are the file's)
+        HPN_HIP(c, hipMemcpyAsync(counts, u->counts.p, (size_t)u->n_ref * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HPN_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    u->open = false;
+    return HPN_OK;
+}
+
+}  // extern "C"

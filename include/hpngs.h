@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 9
+#define HPN_ABI_VERSION 10
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -893,6 +893,64 @@ int hpn_bam_raw_index_dev(hpn_ctx *ctx, const uint8_t *d_raw, const hpn_bgzf_blo
                           uint32_t first_off, const uint32_t *d_status, hpn_raw_info *info);
 int hpn_depth_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw);
 int hpn_window_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw);
+
+/* ---- bamSplitChr: one BAM per target, cut into BGZF blocks as samtools' writer cuts them ------
+ * bamSplitChr.c:129-138 -- bam_fetch(tid, 0, 1 << 29) + samwrite per target -- for a coordinate-sorted file: a target's
+ * records are one slice of the inflated stream, copied verbatim (4 + block_size bytes each) and cut by bam_write1's rule
+ * (bam.c:238 bgzf_flush_try, bgzf.c bgzf_write): with `off` the fill of the open block and s the record's size, the block is
+ * closed first if off + s > 0xff00, the record is appended, and a block that reaches 0xff00 is closed at once -- so a record
+ * of 0xff00 bytes or more runs through blocks of exactly 0xff00.  A target's last block is closed when the target ends.
+ *   hpn_bam_split_begin(n_ref, level0)
+ *   per batch: hpn_bam_raw_index_dev(...), then hpn_bam_split_add_raw_dev(d_raw, last, &info)
+ *              d_raw NULL: no records, only `last` (closes the open block at the end of the file)
+ *   hpn_bam_split_blocks / _payload_dev / _stored_dev    what the call closed
+ *   hpn_bam_split_finish                                  per-target record counts
+ * The closed blocks of a call are listed in file order: off / len = the block's bytes inside the payload buffer
+ * (hpn_bam_split_payload_dev; it holds the bytes of the block left open before in front of the batch's records), crc = their
+ * CRC-32, tid = the target.  A target's last block of a call stays open (unless `last`): its bytes are kept on the device and
+ * the next call's cuts start from its fill.  With level0 != 0 every closed block is also framed on the device as BGZF holding
+ * one stored deflate block (len + 31 bytes: what deflate() makes of it at level 0), one after the other in list order:
+ * hpn_bam_split_stored_dev.  Both buffers are valid until the next hpn_bam_split_* call.
+ * Domain (outside it the reference's answer depends on the index's chunk lists): refID never decreases, with -1 behind every
+ * placed record; pos never decreases inside a target; 0 <= pos < 2^29 and refID < n_ref for placed records.  The first
+ * offending record since _begin is reported -- bad_record (ordinal, -1: none), bad_tid, bad_pos, reason (1 refID out of
+ * range, 2 pos out of range, 3 refID goes backwards, 4 pos goes backwards) -- and the session makes no more blocks.
+ * Synchronous. */
+typedef struct hpn_split_info {
+    uint64_t n_records;      /* records of this batch */
+    uint64_t n_blocks;       /* blocks this call closed */
+    uint64_t payload_bytes;  /* bytes of the payload buffer the closed blocks cover (they lie in [0, payload_bytes)) */
+    uint64_t stored_bytes;   /* size of the stored image (0 unless level0) */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    int32_t tid_first, tid_last; /* targets of the first and last closed block (0, -1: none) */
+    uint32_t reason, open_bytes; /* open_bytes: fill of the block left open */
+} hpn_split_info;
+typedef struct hpn_split_block {
+    uint64_t off;
+    uint32_t len, crc;
+    int32_t tid;
+    uint32_t reserved;
+} hpn_split_block;
+typedef struct hpn_split_result {
+    uint64_t n_records, n_blocks; /* since _begin */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, n_ref;
+} hpn_split_result;
+/* The framing on its own, for any producer of BGZF: spans[k] (host array) = len bytes (1 .. 0xff00) of d_data at off with
+ * CRC-32 crc -> the block's len + 31 bytes at d_image + img_off.  Nothing outside a block's own image is written.  Synchronous. */
+typedef struct hpn_stored_span {
+    uint64_t off, img_off;
+    uint32_t len, crc;
+} hpn_stored_span;
+int hpn_bgzf_stored_dev(hpn_ctx *ctx, const uint8_t *d_data, const hpn_stored_span *spans, uint32_t n_spans, uint8_t *d_image);
+int hpn_bam_split_begin(hpn_ctx *ctx, int32_t n_ref, int level0);
+int hpn_bam_split_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw, int last, hpn_split_info *info);
+int hpn_bam_split_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n); /* *n: blocks of the call from `first` on; HPN_E_CAPACITY if more than cap */
+int hpn_bam_split_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
+int hpn_bam_split_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
+int hpn_bam_split_finish(hpn_ctx *ctx, hpn_split_result *res, uint64_t *counts /* [n_ref] records per target, may be NULL */);
 
 /* ---- multi-GPU reduction of count vectors -----------------------------------
  * One RCCL communicator per context; `unique_id` is the 128-byte ncclUniqueId
