@@ -87,6 +87,14 @@ class SortResult(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64), ("refined", C.c_uint64), ("rounds", C.c_uint32), ("lone_line", C.c_uint32)]
 
 
+class KseqResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_distinct", C.c_uint64), ("out_bytes", C.c_uint64), ("refined", C.c_uint64), ("rounds", C.c_uint32),
+                ("shape", C.c_uint32), ("one_length", C.c_uint32), ("first_len", C.c_uint32), ("other_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+KSEQ_NONE, KSEQ_FASTA, KSEQ_FASTQ = 0, 1, 2
+
+
 class TwobitResult(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64), ("bad_record", C.c_int64), ("seq_len", C.c_uint32), ("packed_len", C.c_uint32)]
 
@@ -119,6 +127,7 @@ class TextPiece(C.Structure):
 TEXT_PIECE_TAIL = 4096
 TEXT_NUL, TEXT_LONG_LINE, TEXT_RAGGED, TEXT_PARTIAL, TEXT_LEN, TEXT_DENSE, TEXT_STALE = 1, 2, 4, 8, 16, 32, 64
 TEXT_SHORT_QUAL = 128
+TEXT_KSEQ = 256
 TEXT_INPLACE_PAD = 8192
 
 
@@ -222,6 +231,10 @@ SYMBOLS = [
     ("hpn_fastq_sort_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
     ("hpn_fastq_sort_finish", _int, [_vp, C.POINTER(SortResult)]),
     ("hpn_fastq_sort_write", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_kseq_begin", _int, [_vp, _u64]),
+    ("hpn_kseq_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
+    ("hpn_kseq_finish", _int, [_vp, C.POINTER(KseqResult)]),
+    ("hpn_kseq_write", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_twobit_pack_begin", _int, [_vp, _u64]),
     ("hpn_twobit_pack_add", _int, [_vp, _vp, _u64, _int, C.POINTER(SortInfo)]),
     ("hpn_twobit_pack_finish", _int, [_vp, C.POINTER(TwobitResult)]),
@@ -307,7 +320,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 10:
+    if L.hpn_abi_version() != 11:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -373,6 +373,35 @@ class Context:
             parts.append(buf[:got.value].tobytes())
             at += got.value
 
+    # ---- kseq input, the first record of every distinct sequence in the sequences' order (map_kseq, kbtree_kseq) ----
+    def kseq_begin(self, max_bytes=0):
+        self._ck(self.L.hpn_kseq_begin(self.h, int(max_bytes)), "hpn_kseq_begin")
+
+    def kseq_add(self, chunk, last=False):
+        """One chunk of FASTA or FASTQ text, cut anywhere, into the session's device store; returns the hpn_sort_info.
+        info.irregular (TEXT_KSEQ: neither of the two shapes the device frames; TEXT_NUL) closes the session."""
+        chunk, n = self._text(chunk)
+        info = _lib.SortInfo()
+        self._ck(self.L.hpn_kseq_add(self.h, _ptr(chunk) if n else None, n, int(bool(last)), C.byref(info)), "hpn_kseq_add")
+        return info
+
+    def kseq_finish(self):
+        res = _lib.KseqResult()
+        self._ck(self.L.hpn_kseq_finish(self.h, C.byref(res)), "hpn_kseq_finish")
+        return res
+
+    def kseq_output(self, slice_bytes=1 << 24):
+        """The whole output text, fetched in slices (hpn_kseq_write)."""
+        parts, at = [], 0
+        buf = np.zeros(max(int(slice_bytes), 1), np.uint8)
+        while True:
+            got = C.c_uint64(0)
+            self._ck(self.L.hpn_kseq_write(self.h, at, _ptr(buf), buf.size, C.byref(got)), "hpn_kseq_write")
+            if not got.value:
+                return b"".join(parts)
+            parts.append(buf[:got.value].tobytes())
+            at += got.value
+
     # ---- the sequences packed to 2 bits per base, and back (fastq2twobit, twoBit2seq) ---------
     def twobit_pack_begin(self, max_bytes=0):
         self._ck(self.L.hpn_twobit_pack_begin(self.h, int(max_bytes)), "hpn_twobit_pack_begin")

@@ -98,6 +98,7 @@ int hpn_ctx_destroy(hpn_ctx *c)
         if (s->p) (void)hipFree(s->p);
     uniq_release(c);
     sort_release(c);
+    kseq_release(c);
     uniqq_release(c);
     usort_release(c);
     twobit_release(c);

@@ -19,6 +19,7 @@ struct hpn_pair_state;   // hpn_pair.hip
 struct hpn_mrle_state;   // hpn_mrle.hip
 struct hpn_rfastqc_state; // hpn_rqcfile.hip
 struct hpn_split_state;  // hpn_split.hip
+struct hpn_kseq_state;   // hpn_kseq.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -107,6 +108,7 @@ struct hpn_ctx {
     hpn_mrle_state *ml = nullptr;   // hpn_mrle_*: the store, the sizes and offsets, the packed, text and shared outputs
     hpn_rfastqc_state *rq = nullptr; // hpn_rfastqc_*: a store per mate, the grouping's arrays, the list's elements
     hpn_split_state *sp = nullptr;   // hpn_bam_split_*: keys, cuts and block list of the batch, the payload, the open block
+    hpn_kseq_state *kq = nullptr;    // hpn_kseq_*: the stream, the normalised store, the framing's arrays, a sort state, the output
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -142,6 +144,7 @@ void pair_release(hpn_ctx *c);   // hpn_pair.hip
 void mrle_release(hpn_ctx *c);   // hpn_mrle.hip
 void rfastqc_release(hpn_ctx *c); // hpn_rqcfile.hip
 void split_release(hpn_ctx *c);  // hpn_split.hip
+void kseq_release(hpn_ctx *c);   // hpn_kseq.hip
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

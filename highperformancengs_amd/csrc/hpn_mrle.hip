@@ -71,7 +71,7 @@ int hpn_mrle_begin(hpn_ctx *c, uint64_t max_bytes)
 int hpn_mrle_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->ml ? &c->ml->s : nullptr, "hpn_mrle", 0, kSortDescBytes, launch_sort_frame, text, nbytes, last, false, info);
+    return session_add(c, c->ml ? &c->ml->s : nullptr, "hpn_mrle", 0, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_mrle_finish(hpn_ctx *c, hpn_mrle_result *res)

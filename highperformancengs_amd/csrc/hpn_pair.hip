@@ -98,7 +98,7 @@ int hpn_fastq_pair_begin(hpn_ctx *c, uint64_t max_bytes)
 int hpn_fastq_pair_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->pr ? &c->pr->s : nullptr, "hpn_fastq_pair", mate, kSortDescBytes, launch_sort_frame, text, nbytes, last, true, info);
+    return session_add(c, c->pr ? &c->pr->s : nullptr, "hpn_fastq_pair", mate, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, true, info);
 }
 
 int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)

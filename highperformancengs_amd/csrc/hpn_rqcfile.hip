@@ -158,7 +158,7 @@ int hpn_rfastqc_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t hash_
 int hpn_rfastqc_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->rq ? &c->rq->s : nullptr, "hpn_rfastqc", mate, kSortDescBytes, launch_sort_frame, text, nbytes, last, false, info);
+    return session_add(c, c->rq ? &c->rq->s : nullptr, "hpn_rfastqc", mate, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_rfastqc_finish(hpn_ctx *c, hpn_rfastqc_result *res)

@@ -16,14 +16,14 @@ struct SortTied {   // kernels/fastq_sort.hip
     u64 *kp;
 };
 // kernels/fastq_sort.hip
-hipError_t launch_sort_key0(const uint8_t *d_text, const void *d_desc, int by_name, uint32_t n, uint64_t *d_key, uint32_t *d_val,
-                            hipStream_t st);
+hipError_t launch_sort_key0(const uint8_t *d_text, const void *d_desc, int by_name, int bytes_only, uint32_t n, uint64_t *d_key,
+                            uint32_t *d_val, hipStream_t st);
 hipError_t launch_sort_bits(const uint64_t *d_key, uint32_t n, uint64_t *d_bits, int n_cu, hipStream_t st);
 hipError_t launch_sort_place0(const void *d_desc, int by_name, const uint32_t *d_val, uint32_t n, uint32_t *d_order, const SortTied &t,
                               hipStream_t st);
 hipError_t launch_sort_heads(const uint64_t *d_word, const uint32_t *d_run, uint32_t m, uint32_t *d_head, hipStream_t st);
 hipError_t launch_sort_settle(const uint8_t *d_text, const SortTied &t, const uint32_t *d_head, const uint32_t *d_gid, uint32_t c,
-                              uint32_t m, uint32_t *d_stay, uint32_t *d_keep, hipStream_t st);
+                              uint32_t m, int bytes_only, uint32_t *d_stay, uint32_t *d_keep, hipStream_t st);
 hipError_t launch_sort_compact(const uint32_t *d_keep, const uint32_t *d_at, const uint32_t *d_head, const uint32_t *d_gid,
                                const SortTied &a, uint32_t m, const SortTied &b, hipStream_t st);
 hipError_t launch_sort_word(const uint8_t *d_text, const SortTied &t, uint32_t c, uint32_t m, uint64_t *d_key, uint32_t *d_val,
@@ -40,12 +40,13 @@ using namespace hpn;
 
 namespace {
 constexpr uint32_t kFirstBytes = 6, kWordBytes = 8, kMaxRounds = 128;   // 6 + 8 * 127 = 1022, the longest line gzgets leaves whole
+constexpr uint32_t kMaxRoundsKseq = 8194;                               // 6 + 8 * 8192 > 65,535, the longest sequence kseq framing keeps
 enum { kSiBits = kInfoOwn };   // the family's words of the info block: two uint64
 }  // namespace
 
 struct hpn_sort_state {
     StoreSession s;
-    int by_name = 0;
+    int by_name = 0, bytes_only = 0;   // bytes_only: the third key mode (hpn_kseq_*), the sequence without its length in front
     Scratch order, key, val, key_tmp, val_tmp, hist, offs, status, word1, val1, word, head, gid, stay, keep, at, size, off, out;
     Scratch t_pos[2], t_ord[2], t_len[2], t_run[2], t_kp[2];
     uint32_t N = 0;
@@ -107,7 +108,7 @@ int settle(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, int cur, const ui
     const SortTied a = tied(u, cur), b = tied(u, cur ^ 1);
     HPN_HIP(c, launch_sort_heads(word, a.run, m, head, c->stream));
     HPN_HIP(c, uniq_scan32(head, gid, m, (u64 *)u->status.p, ticket, err, c->stream));
-    HPN_HIP(c, launch_sort_settle(text, a, head, gid, consumed, m, stay, keep, c->stream));
+    HPN_HIP(c, launch_sort_settle(text, a, head, gid, consumed, m, u->bytes_only, stay, keep, c->stream));
     HPN_HIP(c, uniq_scan32(keep, at, m, (u64 *)u->status.p, ticket, err, c->stream));
     uint32_t n_left = 0;
     HPN_HIP(c, hipMemcpyAsync(&n_left, at + m, 4, hipMemcpyDeviceToHost, c->stream));
@@ -117,11 +118,12 @@ int settle(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, int cur, const ui
     return HPN_OK;
 }
 
-int order_records(hpn_ctx *c, hpn_sort_state *u, hpn_sort_result *res)
+// the N records that `desc` describes in `text`, by the state's key mode, into u->order (the info block is u->s's)
+int order_records(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, const void *desc, hpn_sort_result *res)
 {
     int rc;
     const uint32_t N = u->N;
-    const uint8_t *text = u->s.text(0);
+    const uint32_t max_rounds = u->bytes_only ? kMaxRoundsKseq : kMaxRounds;
     if ((rc = need(c, u->order, (size_t)N * 4)) != HPN_OK) return rc;
     if (!N) return HPN_OK;
     Scratch *per4[] = {&u->val, &u->val1, &u->head, &u->stay, &u->keep, &u->t_pos[0], &u->t_pos[1], &u->t_ord[0], &u->t_ord[1],
@@ -137,13 +139,13 @@ int order_records(hpn_ctx *c, hpn_sort_state *u, hpn_sort_result *res)
     // round 0
     int cur = 0;
     uint32_t m = 0, consumed = kFirstBytes;
-    HPN_HIP(c, launch_sort_key0(text, u->s.m[0].desc.p, u->by_name, N, key, val, c->stream));
+    HPN_HIP(c, launch_sort_key0(text, desc, u->by_name, u->bytes_only, N, key, val, c->stream));
     if ((rc = sort_differing(c, u, N)) != HPN_OK) return rc;
-    HPN_HIP(c, launch_sort_place0(u->s.m[0].desc.p, u->by_name, val, N, order, tied(u, cur), c->stream));
+    HPN_HIP(c, launch_sort_place0(desc, u->by_name, val, N, order, tied(u, cur), c->stream));
     if ((rc = settle(c, u, text, cur, key, consumed, N, &m)) != HPN_OK) return rc;
     res->rounds = 1;
     while (m) {
-        if (res->rounds >= kMaxRounds) return fail(c, HPN_E_HIP, "the refinement did not end within %u rounds", kMaxRounds);
+        if (res->rounds >= max_rounds) return fail(c, HPN_E_HIP, "the refinement did not end within %u rounds", max_rounds);
         cur ^= 1;   // (settle compacted into the other side)
         res->rounds += 1, res->refined += m;
         const SortTied a = tied(u, cur), b = tied(u, cur ^ 1);
@@ -164,6 +166,42 @@ int order_records(hpn_ctx *c, hpn_sort_state *u, hpn_sort_result *res)
 }  // namespace
 
 namespace hpn {
+// The refinement sort for a session of another family (hpn_kseq.hip), by the sequence's bytes alone: a sort state of its own
+// (its arrays and its info block, no store), the order of the n records of `desc` in `text`, and the order's array.
+hpn_sort_state *sort_state_new(hpn_ctx *c)
+{
+    hpn_sort_state *u = new hpn_sort_state;
+    u->bytes_only = 1;
+    if (info_alloc(c, u->s) != HPN_OK) {
+        info_free(u->s);
+        delete u;
+        return nullptr;
+    }
+    return u;
+}
+
+void sort_state_drop(hpn_sort_state *u) { drop_session(u); }
+
+void sort_state_free(hpn_sort_state *u)
+{
+    if (!u) return;
+    drop_session(u);
+    info_free(u->s);
+    delete u;
+}
+
+int sort_state_order(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, const void *desc, uint32_t n, uint32_t *rounds, uint64_t *refined,
+                     const uint32_t **d_order)
+{
+    hpn_sort_result res = {};
+    u->N = n;
+    HPN_HIP(c, hipMemsetAsync(u->s.d_info, 0, kInfoWords * sizeof(uint32_t), c->stream));
+    const int rc = order_records(c, u, text, desc, &res);
+    *rounds = res.rounds, *refined = res.refined;
+    *d_order = (const uint32_t *)u->order.p;
+    return rc;
+}
+
 void sort_release(hpn_ctx *c)
 {
     if (!c->sq) return;
@@ -189,7 +227,7 @@ int hpn_fastq_sort_begin(hpn_ctx *c, int by_name, uint64_t max_bytes)
 int hpn_fastq_sort_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->sq ? &c->sq->s : nullptr, "hpn_fastq_sort", 0, kSortDescBytes, launch_sort_frame, text, nbytes, last, false, info);
+    return session_add(c, c->sq ? &c->sq->s : nullptr, "hpn_fastq_sort", 0, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_fastq_sort_finish(hpn_ctx *c, hpn_sort_result *res)
@@ -209,7 +247,7 @@ int hpn_fastq_sort_finish(hpn_ctx *c, hpn_sort_result *res)
     }
     res->lone_line = framed < u->s.m[0].len ? 1u : 0u;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTally], c->stream));
-    if ((rc = order_records(c, u, res)) != HPN_OK) return rc;
+    if ((rc = order_records(c, u, u->s.text(0), u->s.m[0].desc.p, res)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTally], c->stream));
     c->ev_valid[kFamTally] = true;
     // the output text

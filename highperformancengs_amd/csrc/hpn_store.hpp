@@ -1,5 +1,5 @@
-// hpn_store.hpp -- the device store behind the eight store-backed entry points (hpn_fastq_uniq_*, _uniqq_*, _usort_*, _sort_*, _pair_*,
-// hpn_twobit_pack_*, hpn_mrle_*, hpn_rfastqc_*) and the session around it.  The store: a stream's bytes are appended as they come and framed WHERE THEY
+// hpn_store.hpp -- the device store behind the nine store-backed entry points (hpn_fastq_uniq_*, _uniqq_*, _usort_*, _sort_*, _pair_*,
+// hpn_twobit_pack_*, hpn_mrle_*, hpn_rfastqc_*, hpn_kseq_*) and the session around it.  The store: a stream's bytes are appended as they come and framed WHERE THEY
 // LIE (no carry is copied: the next chunk's framing starts at the first unfinished record), one descriptor per record.  What a
 // descriptor holds is the caller's: it hands in the kernel that writes them (kernels/fastq_uniq.hip: k_uniq_keys,
 // kernels/fastq_sort.hip: k_sort_frame) behind the line index of kernels/fastq_text.hip.  The session: one or two stores under
@@ -17,7 +17,7 @@ uint64_t text_tiles1(uint32_t begin, uint32_t end);
 uint64_t text_tiles2(uint32_t nl_cap);
 // kernels/fastq_sort.hip: the framing behind kernels/sort_desc.hpp
 hipError_t launch_sort_frame(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st);
+                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *user);
 // kernels/fastq_uniq.hip: the scans and the radix sort (radix_sort.hpp)
 hipError_t uniq_scan32(const uint32_t *d_in, uint32_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
 hipError_t uniq_scan64(const uint32_t *d_in, uint64_t *d_out, uint64_t n, u64 *d_status, uint32_t *d_ticket, uint32_t *d_err, hipStream_t st);
@@ -40,9 +40,10 @@ struct RecordStore {
     bool closed = false;
 };
 
-// writes the descriptors of the records that the line index d_nl holds (launched over an upper bound of records)
+// writes the descriptors of the records that the line index d_nl holds (launched over an upper bound of records); `user` is
+// the caller's own (the kernels of the gzgets families take none: nullptr)
 typedef hipError_t (*store_frame_fn)(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                                     void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st);
+                                     void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *user);
 
 inline void release_scratch(Scratch &s)
 {
@@ -82,8 +83,10 @@ inline int need(hpn_ctx *c, Scratch &s, size_t bytes) { return scratch_reserve(c
 
 // One chunk into the store (the caller has checked the chunk's size and the store's limit).  *n_records: records framed by this
 // call; *irregular: HPN_TEXT_* reasons (nothing of the chunk counts then); *close: the session cannot go on (irregular text, an
-// error of the device, 2^31 records) -- the status is the call's.
-inline int store_add(hpn_ctx *c, RecordStore &m, size_t desc_bytes, store_frame_fn frame, const void *text, uint64_t nbytes, int last,
+// error of the device, 2^31 records) -- the status is the call's.  record_lines: the fewest lines a record takes -- the bound
+// the descriptors are sized and `frame` is launched by is the chunk's lines / record_lines (4 for four gzgets per record, 1 for
+// kseq framing, where a FASTA header alone is a record).
+inline int store_add(hpn_ctx *c, RecordStore &m, size_t desc_bytes, store_frame_fn frame, void *user, uint32_t record_lines, const void *text, uint64_t nbytes, int last,
                      uint64_t *n_records, uint32_t *irregular, bool *close)
 {
     *n_records = 0, *irregular = 0, *close = false;
@@ -127,14 +130,14 @@ inline int store_add(hpn_ctx *c, RecordStore &m, size_t desc_bytes, store_frame_
         *irregular = h[kTsFlags], *close = true;
         return HPN_OK;
     }
-    const uint32_t max_records = h[kTsLines] / 4u;
+    const uint32_t max_records = h[kTsLines] / record_lines;
     if (m.n + max_records >= (1ull << 31)) {
         *close = true;
         return fail(c, HPN_E_DOMAIN, "2^31 or more records");
     }
     if ((rc = grow_keep(c, m.desc, (size_t)(m.n + max_records + 1) * desc_bytes, (size_t)m.n * desc_bytes)) != HPN_OK) return rc;
     HPN_HIP(c, frame(slot, (const uint32_t *)c->t_nl.p, begin, end, last, m.pos, (uint8_t *)m.desc.p + (size_t)m.n * desc_bytes, max_records,
-                     c->t_state, c->stream));
+                     c->t_state, c->stream, user));
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamText], c->stream));
     c->ev_valid[kFamText] = true;
     HPN_HIP(c, hipMemcpyAsync(c->h_tstate, c->t_state, kStateWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -217,7 +220,8 @@ inline int session_begin(hpn_ctx *c, StoreSession &s, int n_streams, uint64_t ma
 // own_bytes the fed stream's.  A chunk beyond the limit and an irregular chunk close the session; NULL text and a span beyond
 // 2^31 - 4 KiB do not.
 template <class Info>
-int session_add(hpn_ctx *c, StoreSession *s, const char *api, int mate, size_t desc_bytes, store_frame_fn frame, const void *text,
+int session_add(hpn_ctx *c, StoreSession *s, const char *api, int mate, size_t desc_bytes, store_frame_fn frame, void *user, uint32_t record_lines,
+                const void *text,
                 uint64_t nbytes, int last, bool own_bytes, Info *info)
 {
     if (!s || !s->open || s->finished) return fail(c, HPN_E_STATE, "%s_begin first (or the session was closed by an irregular chunk)", api);
@@ -235,7 +239,7 @@ int session_add(hpn_ctx *c, StoreSession *s, const char *api, int mate, size_t d
         return fail(c, HPN_E_CAPACITY, "the store needs %llu bytes, max_bytes is %llu", (unsigned long long)stored, (unsigned long long)s->limit);
     }
     bool close = false;
-    const int rc = store_add(c, m, desc_bytes, frame, text, nbytes, last, &info->n_records, &info->irregular, &close);
+    const int rc = store_add(c, m, desc_bytes, frame, user, record_lines, text, nbytes, last, &info->n_records, &info->irregular, &close);
     info->store_bytes = own_bytes ? m.len : s->m[0].len + s->m[1].len;
     if (close) s->open = false;
     return rc;

@@ -67,7 +67,7 @@ int hpn_twobit_pack_begin(hpn_ctx *c, uint64_t max_bytes)
 int hpn_twobit_pack_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->tb ? &c->tb->s : nullptr, "hpn_twobit_pack", 0, kSortDescBytes, launch_sort_frame, text, nbytes, last, false, info);
+    return session_add(c, c->tb ? &c->tb->s : nullptr, "hpn_twobit_pack", 0, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_twobit_pack_finish(hpn_ctx *c, hpn_twobit_result *res)

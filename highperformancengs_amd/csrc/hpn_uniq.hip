@@ -61,7 +61,7 @@ int hpn_fastq_uniq_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t ha
 int hpn_fastq_uniq_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->uq ? &c->uq->s : nullptr, "hpn_fastq_uniq", mate, kUniqDescBytes, launch_uniq_keys, text, nbytes, last, false, info);
+    return session_add(c, c->uq ? &c->uq->s : nullptr, "hpn_fastq_uniq", mate, kUniqDescBytes, launch_uniq_keys, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_fastq_uniq_finish(hpn_ctx *c, hpn_uniq_result *res)

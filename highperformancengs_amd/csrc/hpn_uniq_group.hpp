@@ -22,9 +22,9 @@
 namespace hpn {
 // kernels/fastq_uniq.hip
 hipError_t launch_uniq_keys(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                            void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st);
+                            void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *user);
 hipError_t launch_uniqq_keys(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st);
+                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *user);
 hipError_t launch_uniq_names(const uint8_t *t0, const void *d0, const uint8_t *t1, const void *d1, uint32_t n, uint32_t *d_first_bad,
                              hipStream_t st);
 hipError_t launch_uniq_pair(const uint8_t *t0, const void *d0, const uint8_t *t1, const void *d1, int paired, uint32_t n,

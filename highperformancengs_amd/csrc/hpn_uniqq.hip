@@ -132,7 +132,7 @@ int hpn_fastq_uniqq_begin(hpn_ctx *c, uint64_t max_bytes, uint32_t hash_bits)
 int hpn_fastq_uniqq_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->qq ? &c->qq->g.s : nullptr, "hpn_fastq_uniqq", 0, kUniqDescBytes, launch_uniqq_keys, text, nbytes, last, false, info);
+    return session_add(c, c->qq ? &c->qq->g.s : nullptr, "hpn_fastq_uniqq", 0, kUniqDescBytes, launch_uniqq_keys, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_fastq_uniqq_finish(hpn_ctx *c, hpn_uniqq_result *res)

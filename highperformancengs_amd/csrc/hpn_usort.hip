@@ -113,7 +113,7 @@ int hpn_fastq_usort_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes,
     if (!c || !info) return HPN_E_ARG;
     hpn_usort_state *q = c->us;
     const uint64_t span = q && mate == 0 ? q->g.s.m[0].len - q->g.s.m[0].pos + nbytes : 0;   // (what the call frames, when it gets that far)
-    const int rc = session_add(c, q ? &q->g.s : nullptr, "hpn_fastq_usort", mate, kUniqDescBytes, launch_uniqq_keys, text, nbytes, last, false, info);
+    const int rc = session_add(c, q ? &q->g.s : nullptr, "hpn_fastq_usort", mate, kUniqDescBytes, launch_uniqq_keys, nullptr, 4u, text, nbytes, last, false, info);
     // the line index of the stream's last stretch tells whether one open line follows the last record (k_uniq_keys takes it as
     // no record; count_read's gzgets returns it)
     if (rc == HPN_OK && q->g.s.open && last && mate == 0 && span)

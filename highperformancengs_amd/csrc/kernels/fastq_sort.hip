@@ -23,6 +23,11 @@
 //   k_sort_runkey / k_sort_place   the second sort's key, and the write-back.
 //   k_sort_sizes + scan, k_sort_write   the output text, 16 lanes per record (copy_span).
 //
+// A third key mode beside name and sequence (hpn_kseq_*: std::map<std::string>'s order, strcmp): the sequence's bytes alone,
+// zero-padded, without the length in front.  Round 0's key then carries no length (`bytes_only`), and a run is settled only
+// when its neighbours agree in length AS WELL AS in bytes: a key that is a proper prefix of its neighbour stays, and the zero
+// word it gets in the next round puts it in front.
+//
 // Bound: HBM.  Round 0 and the output touch every record; on reads, round 1 touches nearly all of them once more (4^6
 // prefixes) and round 2 a few thousand.  The scattered loads (key0: descriptor then text; word, equal: text) are issued for
 // several records per lane before the first is used.
@@ -77,7 +82,7 @@ __global__ __launch_bounds__(kTxtThreads) void k_sort_frame(const uint8_t *__res
 }
 
 __global__ __launch_bounds__(256) void k_sort_key0(const uint8_t *__restrict__ text, const SortDesc *__restrict__ desc, int by_name,
-                                                   uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ val)
+                                                   int bytes_only, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ val)
 {
     const uint32_t i0 = (blockIdx.x * 256u + threadIdx.x) * kSortItems;
     SortDesc d[kSortItems];
@@ -94,7 +99,7 @@ __global__ __launch_bounds__(256) void k_sort_key0(const uint8_t *__restrict__ t
             const uint32_t len = by_name ? d[k].nlen : d[k].slen, avail = len < 6u ? len : 6u;
             u64 b = __builtin_bswap64(w[k]);
             b = avail ? (b >> (8u * (8u - avail))) << (8u * (8u - avail)) : 0ull;
-            key[i0 + k] = ((u64)len << 48) | (b >> 16);
+            key[i0 + k] = ((u64)(bytes_only ? 0u : len) << 48) | (b >> 16);
             val[i0 + k] = i0 + k;
         }
 }
@@ -179,11 +184,16 @@ __device__ __forceinline__ bool span_differs(const uint8_t *a, const uint8_t *b,
 // when two neighbours of the run differ behind byte c (a run shorter than that, or of equal keys, is settled).
 __global__ __launch_bounds__(256) void k_sort_equal(const uint8_t *__restrict__ text, const u64 *__restrict__ kp,
                                                     const uint32_t *__restrict__ len, const uint32_t *__restrict__ head,
-                                                    const uint32_t *__restrict__ gid, uint32_t c, uint32_t m, uint32_t *__restrict__ stay)
+                                                    const uint32_t *__restrict__ gid, uint32_t c, uint32_t m, int bytes_only,
+                                                    uint32_t *__restrict__ stay)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= m || j == 0u || head[j]) return;
     const uint32_t L = len[j];
+    if (bytes_only && len[j - 1u] != L) {   // one is a proper prefix of the other so far: the padding decides
+        stay[gid[j] - 1u] = 1u;
+        return;
+    }
     if (L <= c) return;
     if (span_differs(text + kp[j] + c, text + kp[j - 1u] + c, L - c)) stay[gid[j] - 1u] = 1u;
 }
@@ -307,17 +317,18 @@ static inline unsigned blocks256(uint32_t n) { return n ? (n + 255u) / 256u : 1u
 static inline unsigned blocks_items(uint32_t n) { return blocks256((n + kSortItems - 1u) / kSortItems); }
 
 hipError_t launch_sort_frame(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st)
+                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *)
 {
     hipLaunchKernelGGL(k_sort_frame, dim3(max_records / kTxtThreads + 1u), dim3(kTxtThreads), 0, st, d_slot, d_nl, begin, end, last,
                        (u64)origin, (SortDesc *)d_desc, d_state);
     return hipGetLastError();
 }
 
-hipError_t launch_sort_key0(const uint8_t *d_text, const void *d_desc, int by_name, uint32_t n, uint64_t *d_key, uint32_t *d_val,
-                            hipStream_t st)
+hipError_t launch_sort_key0(const uint8_t *d_text, const void *d_desc, int by_name, int bytes_only, uint32_t n, uint64_t *d_key,
+                            uint32_t *d_val, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_sort_key0, dim3(blocks_items(n)), dim3(256), 0, st, d_text, (const SortDesc *)d_desc, by_name, n, d_key, d_val);
+    hipLaunchKernelGGL(k_sort_key0, dim3(blocks_items(n)), dim3(256), 0, st, d_text, (const SortDesc *)d_desc, by_name, bytes_only, n, d_key,
+                       d_val);
     return hipGetLastError();
 }
 
@@ -348,11 +359,11 @@ hipError_t launch_sort_heads(const uint64_t *d_word, const uint32_t *d_run, uint
 
 // d_stay: one word per run (at most m), zeroed here; d_keep[j]: element j's run goes on
 hipError_t launch_sort_settle(const uint8_t *d_text, const SortTied &t, const uint32_t *d_head, const uint32_t *d_gid, uint32_t c,
-                              uint32_t m, uint32_t *d_stay, uint32_t *d_keep, hipStream_t st)
+                              uint32_t m, int bytes_only, uint32_t *d_stay, uint32_t *d_keep, hipStream_t st)
 {
     hipError_t e = hipMemsetAsync(d_stay, 0, (size_t)m * sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sort_equal, dim3(blocks256(m)), dim3(256), 0, st, d_text, t.kp, t.len, d_head, d_gid, c, m, d_stay);
+    hipLaunchKernelGGL(k_sort_equal, dim3(blocks256(m)), dim3(256), 0, st, d_text, t.kp, t.len, d_head, d_gid, c, m, bytes_only, d_stay);
     hipLaunchKernelGGL(k_sort_keep, dim3(blocks256(m)), dim3(256), 0, st, d_head, d_gid, d_stay, m, d_keep);
     return hipGetLastError();
 }

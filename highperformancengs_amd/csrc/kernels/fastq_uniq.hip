@@ -381,7 +381,7 @@ __global__ __launch_bounds__(kTxtThreads) void k_uniq_write(const uint8_t *__res
 static inline unsigned blocks256(uint32_t n) { return n ? (n + 255u) / 256u : 1u; }
 
 hipError_t launch_uniq_keys(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                            void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st)
+                            void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *)
 {
     hipLaunchKernelGGL(k_uniq_keys<true>, dim3(max_records / kTxtThreads + 1u), dim3(kTxtThreads), 0, st, d_slot, d_nl, begin, end, last,
                        (u64)origin, (UniqDesc *)d_desc, d_state);
@@ -389,7 +389,7 @@ hipError_t launch_uniq_keys(const uint8_t *d_slot, const uint32_t *d_nl, uint32_
 }
 
 hipError_t launch_uniqq_keys(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st)
+                             void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *)
 {
     hipLaunchKernelGGL(k_uniq_keys<false>, dim3(max_records / kTxtThreads + 1u), dim3(kTxtThreads), 0, st, d_slot, d_nl, begin, end, last,
                        (u64)origin, (UniqDesc *)d_desc, d_state);

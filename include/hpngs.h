@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 10
+#define HPN_ABI_VERSION 11
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -227,6 +227,7 @@ typedef struct hpn_text_info {
                                   earlier lines left in its buffer; the host framer reproduces that) */
 #define HPN_TEXT_SHORT_QUAL 128u /* uniq: quality line two or more bytes shorter than the sequence (the reference sums
                                   bytes outside its buffer) */
+#define HPN_TEXT_KSEQ 256u     /* kseq: the text has neither of the two shapes the device frames (hpn_kseq_*) */
 /* The writable bytes hpn_fastq_text_count_inplace needs in front of the text it frames where it lies. */
 #define HPN_TEXT_INPLACE_PAD 8192u
 
@@ -654,6 +655,57 @@ int hpn_rfastqc_begin(hpn_ctx *ctx, int paired, uint64_t max_bytes, uint32_t has
 int hpn_rfastqc_add(hpn_ctx *ctx, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
 int hpn_rfastqc_finish(hpn_ctx *ctx, hpn_rfastqc_result *result);
 int hpn_rfastqc_read(hpn_ctx *ctx, int which, int mate, uint64_t first_elem, void *out, uint64_t cap_elems, uint64_t *got);
+
+/* ---- map_kseq.cpp / kbtree_kseq.c: kseq input, the first record of every distinct sequence, in the sequences' order -----
+ * The text is framed as the two programs' kseq_read frames it (klib/kseq.h over a kseq_t that is NEW for every record): a
+ * header starts at the next '>' or '@' -- at ANY byte, because the new kseq_t has forgotten that the sequence loop consumed
+ * the next header's first byte; the name runs to the first isspace byte; unless that byte is '\n' the rest of the line is the
+ * comment (a trailing '\r' dropped when the comment is longer than one byte); sequence lines follow up to a line that starts
+ * with '>', '+' or '@', empty lines skipped, after every appended line a trailing '\r' dropped when the accumulated length is
+ * above 1; behind a '+' line quality lines are appended until they reach the sequence's length.  The device frames two shapes:
+ *
+ *   FASTQ  four lines per record and a line count divisible by 4: line 0 starts with '@', line 1 is not empty and does not
+ *          start with '>', '+' or '@', line 2 starts with '+', line 3 has line 1's length (both after the '\r' rule).
+ *   FASTA  the stream's first byte is '>', no line starts with '@' or '+', the last line is no header without its '\n'.
+ *          Every line that starts with '>' opens a block.  kseq_read, coming from a FASTA record, looks for the next '>' or
+ *          '@' behind the first byte of the NEXT block: the blocks 0, 2, 4, ... are the records, and a block 1, 3, 5, ... that
+ *          holds a '>' or '@' behind its first byte is not regular.
+ *   In both: no NUL byte, no header line, joined sequence or "name comment" beyond 65,535 bytes.
+ *
+ * Anything else -- wrapped FASTQ, mixed '>' and '@' records, a truncated tail, text in front of the first header -- is
+ * reported as HPN_TEXT_KSEQ in info->irregular and closes the session (host/kseq_read.hpp reads such text on the host).
+ * Records are copied into a normalised store as "name comment\nsequence\n[quality]" with "(null)" where the programs print a
+ * NULL comment, ordered by the sequence's bytes as unsigned (a prefix first: strcmp on text without NUL) with equal ones in
+ * input order, and the first of every run of equal sequences is written as "name comment\nseq\n+\nqual\n", "(null)" for the
+ * quality a FASTA record does not have.
+ *
+ *   hpn_kseq_begin   opens a session (closing the context's earlier one and releasing its arrays, the ordering's included).  max_bytes: as for hpn_fastq_uniq_begin.
+ *   hpn_kseq_add     one chunk, cut anywhere (inside a header, between the lines of a wrapped sequence, behind a '\r'); host or
+ *                    device pointer; `last` closes the stream.  The unfinished record stays unframed until more bytes or
+ *                    `last` arrive; one that has already joined more than 65,535 bytes, or an unframed span of 2^31 - 4 KiB bytes,
+ *                    is HPN_TEXT_KSEQ at once.  A chunk the framing has no memory for closes the session (HPN_E_NOMEM).
+ *                    HPN_E_CAPACITY and HPN_E_DOMAIN (2^31 or more records) as for hpn_fastq_uniq_add.
+ *   hpn_kseq_finish  after the last chunk: orders, picks every run's first record, formats; fills *result.
+ *   hpn_kseq_write   copies up to `cap` bytes of the output (result->out_bytes in all), from byte `offset` on, to `out`. */
+#define HPN_KSEQ_NONE 0u  /* no byte seen */
+#define HPN_KSEQ_FASTA 1u
+#define HPN_KSEQ_FASTQ 2u
+typedef struct hpn_kseq_result {
+    uint64_t n_records;  /* records read */
+    uint64_t n_distinct; /* distinct sequences: what the programs write to stderr */
+    uint64_t out_bytes;  /* bytes of the output */
+    uint64_t refined;    /* records that went through refinement rounds, summed over the rounds */
+    uint32_t rounds;     /* radix rounds of the ordering (1: the first 6 bytes decided everything) */
+    uint32_t shape;      /* HPN_KSEQ_* */
+    uint32_t one_length; /* 1: every sequence has one length (or there is none) */
+    uint32_t first_len;  /* the first record's sequence length, and ... */
+    uint32_t other_len;  /* ... with one_length 0, the length of the first record that differs from it */
+    uint32_t reserved;
+} hpn_kseq_result;
+int hpn_kseq_begin(hpn_ctx *ctx, uint64_t max_bytes);
+int hpn_kseq_add(hpn_ctx *ctx, const void *text, uint64_t nbytes, int last, hpn_sort_info *info);
+int hpn_kseq_finish(hpn_ctx *ctx, hpn_kseq_result *result);
+int hpn_kseq_write(hpn_ctx *ctx, uint64_t offset, void *out, uint64_t cap, uint64_t *written);
 
 /* ---- ONE text stream framed by several contexts (one per GPU): pieces ----------------------------
  * Record-block sharding of a single FASTQ input (the reference's parallelism stops at
