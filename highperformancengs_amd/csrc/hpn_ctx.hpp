@@ -1,6 +1,7 @@
 // hpn_ctx.hpp -- the per-GPU context behind the C ABI (include/hpngs.h).
 #pragma once
 #include "host/knobs.hpp"
+#include <memory>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -10,16 +11,6 @@
 #include "hpngs.h"
 
 struct hpn_ctx;
-struct hpn_uniq_state;   // hpn_uniq.hip
-struct hpn_sort_state;   // hpn_sort.hip
-struct hpn_uniqq_state;  // hpn_uniqq.hip
-struct hpn_usort_state;  // hpn_usort.hip
-struct hpn_twobit_state; // hpn_twobit.hip
-struct hpn_pair_state;   // hpn_pair.hip
-struct hpn_mrle_state;   // hpn_mrle.hip
-struct hpn_rfastqc_state; // hpn_rqcfile.hip
-struct hpn_split_state;  // hpn_split.hip
-struct hpn_kseq_state;   // hpn_kseq.hip
 namespace hpn {
 typedef unsigned long long u64;
 
@@ -33,11 +24,36 @@ int tally_launch(hpn_ctx *c, const uint8_t *d_qual, const uint8_t *d_base, const
 hipError_t launch_synth_fastq(uint64_t seed, uint64_t first, uint64_t n, uint32_t len, uint8_t *d_qual,
                               uint8_t *d_base, uint64_t *d_off, int n_cu, hipStream_t st);
 
-// A device buffer that only ever grows (staging for the host-buffer entry points).
+// A device buffer that only ever grows (staging for the host-buffer entry points).  It owns what it holds: move-only, freed
+// with its owner.
 struct Scratch {
     void *p = nullptr;
     size_t cap = 0;
+    Scratch() = default;
+    Scratch(Scratch &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    Scratch &operator=(Scratch &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~Scratch() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
 };
+
+// What a session family (hpn_fastq_uniq_*, ..., hpn_bam_split_*) keeps between its calls: the context owns one per family, made
+// on first use.  A family's state names its slot as `kSlot`; a new family adds its slot here and nothing else outside its file.
+struct FamilyState {
+    virtual ~FamilyState() = default;
+};
+enum { kStUniq = 0, kStSort, kStUniqq, kStUsort, kStTwobit, kStPair, kStMrle, kStRfastqc, kStSplit, kStKseq, kStCount };
 
 enum { kFamTally = 0, kFamTrim = 1, kFamDepth = 2, kFamWindow = 3, kFamText = 4, kFamInflate = 5, kFamRaw = 6, kFamRawFields = 7, kFamCount = 8 };
 
@@ -99,16 +115,7 @@ struct hpn_ctx {
     uint32_t gz_n_chunks = 0, gz_sym_cap = 0;
     uint64_t r_n = 0;
     bool r_fields = false;  // the SoA view of the current index has been gathered
-    hpn_uniq_state *uq = nullptr;   // hpn_fastq_uniq_*: the store, the descriptors, the sorts' arrays
-    hpn_sort_state *sq = nullptr;   // hpn_fastq_sort_*: the same for the whole-file sort
-    hpn_uniqq_state *qq = nullptr;  // hpn_fastq_uniqq_*: a uniq session of its own and the members' placement
-    hpn_usort_state *us = nullptr;  // hpn_fastq_usort_*: a uniq session of its own, the 64-bit djb2 and the count order
-    hpn_twobit_state *tb = nullptr; // hpn_twobit_pack_*: the store, the sizes and offsets, the packed output
-    hpn_pair_state *pr = nullptr;   // hpn_fastq_pair_*: a store per mate, the pairing and its certificate, the four outputs
-    hpn_mrle_state *ml = nullptr;   // hpn_mrle_*: the store, the sizes and offsets, the packed, text and shared outputs
-    hpn_rfastqc_state *rq = nullptr; // hpn_rfastqc_*: a store per mate, the grouping's arrays, the list's elements
-    hpn_split_state *sp = nullptr;   // hpn_bam_split_*: keys, cuts and block list of the batch, the payload, the open block
-    hpn_kseq_state *kq = nullptr;    // hpn_kseq_*: the stream, the normalised store, the framing's arrays, a sort state, the output
+    std::unique_ptr<hpn::FamilyState> family[hpn::kStCount];   // the session families' states (hpn::state<T>)
     // RCCL
     void *comm = nullptr;
     char err[512] = {0};
@@ -135,16 +142,18 @@ inline int fail(hpn_ctx *c, int status, const char *fmt, ...)
                              __FILE__, __LINE__);                                             \
     } while (0)
 
-void uniq_release(hpn_ctx *c);   // hpn_uniq.hip
-void sort_release(hpn_ctx *c);   // hpn_sort.hip
-void uniqq_release(hpn_ctx *c);  // hpn_uniqq.hip
-void usort_release(hpn_ctx *c);  // hpn_usort.hip
-void twobit_release(hpn_ctx *c); // hpn_twobit.hip
-void pair_release(hpn_ctx *c);   // hpn_pair.hip
-void mrle_release(hpn_ctx *c);   // hpn_mrle.hip
-void rfastqc_release(hpn_ctx *c); // hpn_rqcfile.hip
-void split_release(hpn_ctx *c);  // hpn_split.hip
-void kseq_release(hpn_ctx *c);   // hpn_kseq.hip
+// the context's state of family T (nullptr before the family's first call), and the same made on first use
+template <class T>
+T *state(hpn_ctx *c)
+{
+    return static_cast<T *>(c->family[T::kSlot].get());
+}
+template <class T>
+T *state_make(hpn_ctx *c)
+{
+    if (!c->family[T::kSlot]) c->family[T::kSlot].reset(new T);
+    return state<T>(c);
+}
 
 inline int scratch_reserve(hpn_ctx *c, Scratch &s, size_t bytes)
 {

@@ -28,10 +28,14 @@ enum { kMlBad = kInfoOwn };   // the family's word of the info block
 enum { kPacked = HPN_MRLE_PACKED, kText = HPN_MRLE_TEXT, kShared = HPN_MRLE_SHARED };   // (plain names: HPN_HIP quotes its call in the message)
 }  // namespace
 
-struct hpn_mrle_state {
-    StoreSession s;
+struct hpn_mrle_work {   // what a new session must not inherit
     Scratch psize, tsize, flag, poff, toff, status, out[3];   // out: by HPN_MRLE_*
     uint64_t out_total[3] = {0, 0, 0};
+};
+
+struct hpn_mrle_state : FamilyState, hpn_mrle_work {
+    static constexpr int kSlot = kStMrle;
+    StoreSession s;
 };
 
 namespace {
@@ -39,23 +43,10 @@ namespace {
 void drop_session(hpn_mrle_state *u)
 {
     session_drop(u->s);
-    Scratch *ss[] = {&u->psize, &u->tsize, &u->flag, &u->poff, &u->toff, &u->status, &u->out[0], &u->out[1], &u->out[2]};
-    for (Scratch *s : ss) release_scratch(*s);
-    u->out_total[0] = u->out_total[1] = u->out_total[2] = 0;
+    static_cast<hpn_mrle_work &>(*u) = hpn_mrle_work();
 }
 
 }  // namespace
-
-namespace hpn {
-void mrle_release(hpn_ctx *c)
-{
-    if (!c->ml) return;
-    drop_session(c->ml);
-    info_free(c->ml->s);
-    delete c->ml;
-    c->ml = nullptr;
-}
-}  // namespace hpn
 
 extern "C" {
 
@@ -63,21 +54,22 @@ int hpn_mrle_begin(hpn_ctx *c, uint64_t max_bytes)
 {
     if (!c) return HPN_E_ARG;
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->ml) c->ml = new hpn_mrle_state;
-    drop_session(c->ml);
-    return session_begin(c, c->ml->s, 1, max_bytes);
+    hpn_mrle_state *u = state_make<hpn_mrle_state>(c);
+    drop_session(u);
+    return session_begin(c, u->s, 1, max_bytes);
 }
 
 int hpn_mrle_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->ml ? &c->ml->s : nullptr, "hpn_mrle", 0, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, false, info);
+    hpn_mrle_state *u = state<hpn_mrle_state>(c);
+    return session_add(c, u ? &u->s : nullptr, "hpn_mrle", 0, kSortDescBytes, frame_by<launch_sort_frame>, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_mrle_finish(hpn_ctx *c, hpn_mrle_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_mrle_state *u = c->ml;
+    hpn_mrle_state *u = state<hpn_mrle_state>(c);
     int rc;
     if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_mrle", kSortDescBytes)) != HPN_OK) return rc;
     memset(res, 0, sizeof *res);
@@ -95,17 +87,17 @@ int hpn_mrle_finish(hpn_ctx *c, hpn_mrle_result *res)
     const uint8_t *text = u->s.text(0);
     const void *desc = u->s.m[0].desc.p;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
-    HPN_HIP(c, launch_mrle_sizes(text, desc, N, (uint32_t *)u->psize.p, (uint32_t *)u->tsize.p, (uint8_t *)u->flag.p, u->s.d_info + kMlBad, c->n_cu,
+    HPN_HIP(c, launch_mrle_sizes(text, desc, N, (uint32_t *)u->psize.p, (uint32_t *)u->tsize.p, (uint8_t *)u->flag.p, u->s.info.d + kMlBad, c->n_cu,
                                  c->stream));
     uint64_t total[3] = {0, 0, 0};
-    if ((rc = scan_sizes(c, u->s, u->status, u->psize, u->poff, N, &total[kPacked])) != HPN_OK) return rc;   // (fetches the info block)
-    if (u->s.h_info[kMlBad] != 0xffffffffu) {
-        const uint32_t bad = u->s.h_info[kMlBad];
+    if ((rc = scan_sizes(c, u->s.info, u->status, u->psize, u->poff, N, &total[kPacked])) != HPN_OK) return rc;   // (fetches the info block)
+    if (u->s.info.h[kMlBad] != 0xffffffffu) {
+        const uint32_t bad = u->s.info.h[kMlBad];
         res->bad_record = (int64_t)bad;
         drop_session(u);
         return fail(c, HPN_E_DOMAIN, "record %u (0-based) has a quality byte outside #/7<BF: the reference indexes an 8-entry table at 255 there", bad);
     }
-    if ((rc = scan_sizes(c, u->s, u->status, u->tsize, u->toff, N, &total[kText])) != HPN_OK) return rc;
+    if ((rc = scan_sizes(c, u->s.info, u->status, u->tsize, u->toff, N, &total[kText])) != HPN_OK) return rc;
     total[kShared] = mrle_shared_bytes(total[kPacked], total[kText]);
     for (int k = 0; k < 3; ++k)
         if ((rc = need(c, u->out[k], total[k])) != HPN_OK) return rc;
@@ -126,7 +118,7 @@ int hpn_mrle_finish(hpn_ctx *c, hpn_mrle_result *res)
 int hpn_mrle_write(hpn_ctx *c, int which, uint64_t offset, void *out, uint64_t cap, uint64_t *written)
 {
     if (!c || !written) return HPN_E_ARG;
-    hpn_mrle_state *u = c->ml;
+    hpn_mrle_state *u = state<hpn_mrle_state>(c);
     const int rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_mrle", written);
     if (rc != HPN_OK) return rc;
     if (which < kPacked || which > kShared) return fail(c, HPN_E_ARG, "output %d (0 packed, 1 text, 2 shared)", which);

@@ -32,10 +32,14 @@ namespace {
 enum { kPrFail = kInfoOwn };   // the family's word of the info block
 }  // namespace
 
-struct hpn_pair_state {
-    StoreSession s;
+struct hpn_pair_work {   // what a new session must not inherit
     Scratch klen, mate, flag[2], rank[2], pair[2], size[2], off[2], status, out[4];
     uint64_t out_total[4] = {0, 0, 0, 0};
+};
+
+struct hpn_pair_state : FamilyState, hpn_pair_work {
+    static constexpr int kSlot = kStPair;
+    StoreSession s;
 };
 
 namespace {
@@ -43,10 +47,7 @@ namespace {
 void drop_session(hpn_pair_state *u)
 {
     session_drop(u->s);
-    Scratch *ss[] = {&u->klen,    &u->mate,    &u->flag[0], &u->flag[1], &u->rank[0], &u->rank[1], &u->pair[0], &u->pair[1], &u->size[0],
-                     &u->size[1], &u->off[0],  &u->off[1],  &u->status,  &u->out[0],  &u->out[1],  &u->out[2],  &u->out[3]};
-    for (Scratch *s : ss) release_scratch(*s);
-    for (uint64_t &t : u->out_total) t = 0;
+    static_cast<hpn_pair_work &>(*u) = hpn_pair_work();
 }
 
 // flags, ranks, the pair list and the one comparison per record over the proposal in u->mate.  *bad: 0xffffffff when the
@@ -58,31 +59,20 @@ int verify(hpn_ctx *c, hpn_pair_state *u, uint32_t nA, uint32_t nB, uint64_t *n_
     const uint32_t n[2] = {nA, nB};
     HPN_HIP(c, launch_pair_flags((const uint32_t *)u->mate.p, nA, nB, fl[0], fl[1], c->stream));
     for (int s = 0; s < 2; ++s) {
-        if (n[s]) HPN_HIP(c, uniq_scan64(fl[s], rk[s], n[s], (u64 *)u->status.p, u->s.ticket(), u->s.err(), c->stream));
+        if (n[s]) HPN_HIP(c, uniq_scan64(fl[s], rk[s], n[s], (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(), c->stream));
         else HPN_HIP(c, hipMemsetAsync(rk[s], 0, 8, c->stream));
     }
     HPN_HIP(c, launch_pair_scatter((const uint32_t *)u->mate.p, rk[0], nA, (uint32_t *)u->pair[0].p, (uint32_t *)u->pair[1].p, c->stream));
     HPN_HIP(c, launch_pair_verify(u->s.text(0), u->s.m[0].desc.p, (const uint32_t *)u->klen.p, nA, u->s.text(1), u->s.m[1].desc.p, nB,
                                   (const uint32_t *)u->mate.p, rk[0], fl[1], rk[1], (const uint32_t *)u->pair[0].p, (const uint32_t *)u->pair[1].p,
-                                  u->s.d_info + kPrFail, c->n_cu, c->stream));
+                                  u->s.info.d + kPrFail, c->n_cu, c->stream));
     HPN_HIP(c, hipMemcpyAsync(n_pairs, rk[0] + nA, 8, hipMemcpyDeviceToHost, c->stream));
-    const int rc = info_fetch(c, u->s);
-    *bad = u->s.h_info[kPrFail];
+    const int rc = u->s.info.fetch(c);
+    *bad = u->s.info.h[kPrFail];
     return rc;
 }
 
 }  // namespace
-
-namespace hpn {
-void pair_release(hpn_ctx *c)
-{
-    if (!c->pr) return;
-    drop_session(c->pr);
-    info_free(c->pr->s);
-    delete c->pr;
-    c->pr = nullptr;
-}
-}  // namespace hpn
 
 extern "C" {
 
@@ -90,21 +80,22 @@ int hpn_fastq_pair_begin(hpn_ctx *c, uint64_t max_bytes)
 {
     if (!c) return HPN_E_ARG;
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->pr) c->pr = new hpn_pair_state;
-    drop_session(c->pr);
-    return session_begin(c, c->pr->s, 2, max_bytes);
+    hpn_pair_state *u = state_make<hpn_pair_state>(c);
+    drop_session(u);
+    return session_begin(c, u->s, 2, max_bytes);
 }
 
 int hpn_fastq_pair_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->pr ? &c->pr->s : nullptr, "hpn_fastq_pair", mate, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, true, info);
+    hpn_pair_state *u = state<hpn_pair_state>(c);
+    return session_add(c, u ? &u->s : nullptr, "hpn_fastq_pair", mate, kSortDescBytes, frame_by<launch_sort_frame>, nullptr, 4u, text, nbytes, last, true, info);
 }
 
 int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_pair_state *u = c->pr;
+    hpn_pair_state *u = state<hpn_pair_state>(c);
     int rc;
     if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_pair", kSortDescBytes)) != HPN_OK) return rc;
     memset(res, 0, sizeof *res);
@@ -157,7 +148,7 @@ int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)
         HPN_HIP(c, launch_pair_sizes(u->s.m[s].desc.p, (const uint32_t *)u->flag[s].p, n[s], (uint32_t *)u->size[0].p, (uint32_t *)u->size[1].p, c->stream));
         uint64_t sum[2] = {0, 0};
         for (int col = 0; col < 2; ++col)
-            if ((rc = scan_sizes(c, u->s, u->status, u->size[col], u->off[col], n[s], &sum[col])) != HPN_OK) return rc;
+            if ((rc = scan_sizes(c, u->s.info, u->status, u->size[col], u->off[col], n[s], &sum[col])) != HPN_OK) return rc;
         for (int col = 0; col < 2; ++col) {
             if ((rc = need(c, u->out[2 * s + col], sum[col])) != HPN_OK) return rc;
             u->out_total[2 * s + col] = res->out_bytes[2 * s + col] = sum[col];
@@ -167,7 +158,7 @@ int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)
     }
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
     c->ev_valid[kFamTrim] = true;
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
     u->s.finished = true;
     return HPN_OK;
 }
@@ -175,7 +166,7 @@ int hpn_fastq_pair_finish(hpn_ctx *c, hpn_pair_result *res)
 int hpn_fastq_pair_write(hpn_ctx *c, int which_output, uint64_t offset, void *out, uint64_t cap, uint64_t *written)
 {
     if (!c || !written) return HPN_E_ARG;
-    hpn_pair_state *u = c->pr;
+    hpn_pair_state *u = state<hpn_pair_state>(c);
     const int rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_pair", written);
     if (rc != HPN_OK) return rc;
     if (which_output < 0 || which_output > 3) return fail(c, HPN_E_ARG, "which_output is %d (0 .. 3)", which_output);

@@ -43,13 +43,17 @@ constexpr size_t kAccBytes = (size_t)HPN_TALLY_WORDS * sizeof(uint64_t), kAccBad
 constexpr size_t kQualityElems = (size_t)HPN_QUAL_ROWS * kRqcMaxLen, kNucleotideElems = (size_t)HPN_NUC_CODES * kRqcMaxLen;
 }  // namespace
 
-struct hpn_rfastqc_state {
-    StoreSession s;
-    int paired = 0;
-    uint32_t hash_bits = 0;
+struct hpn_rfastqc_work {   // what a new session must not inherit
     Scratch hash, order, klen, flag, gid, start, key, key_tmp, val_tmp, hist, offs, status, ssz[2], qsz[2], soff[2], qoff[2], seq, qual, acc;
     Scratch out[2][kArrays];          // by mate and HPN_RFASTQC_*; the duplicate counts are out[0][kDup]
     uint64_t elems[2][kArrays] = {};
+};
+
+struct hpn_rfastqc_state : FamilyState, hpn_rfastqc_work {
+    static constexpr int kSlot = kStRfastqc;
+    StoreSession s;
+    int paired = 0;
+    uint32_t hash_bits = 0;
 };
 
 namespace {
@@ -57,11 +61,7 @@ namespace {
 void drop_session(hpn_rfastqc_state *u)
 {
     session_drop(u->s);
-    Scratch *ss[] = {&u->hash, &u->order, &u->klen, &u->flag, &u->gid, &u->start, &u->key, &u->key_tmp, &u->val_tmp, &u->hist, &u->offs, &u->status,
-                     &u->ssz[0], &u->ssz[1], &u->qsz[0], &u->qsz[1], &u->soff[0], &u->soff[1], &u->qoff[0], &u->qoff[1], &u->seq, &u->qual, &u->acc};
-    for (Scratch *s : ss) release_scratch(*s);
-    for (int k = 0; k < 2; ++k)
-        for (int w = 0; w < kArrays; ++w) release_scratch(u->out[k][w]), u->elems[k][w] = 0;
+    static_cast<hpn_rfastqc_work &>(*u) = hpn_rfastqc_work();
 }
 
 int rq_sort(hpn_ctx *c, hpn_rfastqc_state *u, uint64_t *keys, uint32_t *vals, uint32_t n, int end_bit)
@@ -73,7 +73,7 @@ int rq_sort(hpn_ctx *c, hpn_rfastqc_state *u, uint64_t *keys, uint32_t *vals, ui
         (rc = need(c, u->status, uniq_scan_tiles(hw > n ? hw : n) * 8)) != HPN_OK)
         return rc;
     HPN_HIP(c, uniq_sort_pairs(keys, vals, n, 0, end_bit, (uint64_t *)u->key_tmp.p, (uint32_t *)u->val_tmp.p, (uint32_t *)u->hist.p,
-                               (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.ticket(), u->s.err(), c->stream));
+                               (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(), c->stream));
     return HPN_OK;
 }
 
@@ -131,17 +131,6 @@ int refuse(hpn_ctx *c, hpn_rfastqc_state *u, hpn_rfastqc_result *res, uint32_t b
 
 }  // namespace
 
-namespace hpn {
-void rfastqc_release(hpn_ctx *c)
-{
-    if (!c->rq) return;
-    drop_session(c->rq);
-    info_free(c->rq->s);
-    delete c->rq;
-    c->rq = nullptr;
-}
-}  // namespace hpn
-
 extern "C" {
 
 int hpn_rfastqc_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t hash_bits)
@@ -149,22 +138,23 @@ int hpn_rfastqc_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t hash_
     if (!c) return HPN_E_ARG;
     if (hash_bits > 63) return fail(c, HPN_E_ARG, "hash_bits %u (0 = all 64, or 1 .. 63)", hash_bits);
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->rq) c->rq = new hpn_rfastqc_state;
-    drop_session(c->rq);
-    c->rq->paired = paired ? 1 : 0, c->rq->hash_bits = hash_bits;
-    return session_begin(c, c->rq->s, paired ? 2 : 1, max_bytes);
+    hpn_rfastqc_state *u = state_make<hpn_rfastqc_state>(c);
+    drop_session(u);
+    u->paired = paired ? 1 : 0, u->hash_bits = hash_bits;
+    return session_begin(c, u->s, paired ? 2 : 1, max_bytes);
 }
 
 int hpn_rfastqc_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->rq ? &c->rq->s : nullptr, "hpn_rfastqc", mate, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, false, info);
+    hpn_rfastqc_state *u = state<hpn_rfastqc_state>(c);
+    return session_add(c, u ? &u->s : nullptr, "hpn_rfastqc", mate, kSortDescBytes, frame_by<launch_sort_frame>, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_rfastqc_finish(hpn_ctx *c, hpn_rfastqc_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_rfastqc_state *u = c->rq;
+    hpn_rfastqc_state *u = state<hpn_rfastqc_state>(c);
     int rc;
     if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_rfastqc", kSortDescBytes)) != HPN_OK) return rc;
     memset(res, 0, sizeof *res);
@@ -196,7 +186,7 @@ int hpn_rfastqc_finish(hpn_ctx *c, hpn_rfastqc_result *res)
     }
 
     // ---- the domain, lengths first: sizes, Length[], the offsets of the gathered lines
-    uint32_t *info = u->s.d_info + kRqBad;
+    uint32_t *info = u->s.info.d + kRqBad;
     HPN_HIP(c, hipMemsetAsync(info, 0xff, sizeof(uint32_t), c->stream));
     uint64_t stotal[2] = {0, 0}, qtotal[2] = {0, 0};
     for (int k = 0; k < mates; ++k) {
@@ -207,18 +197,18 @@ int hpn_rfastqc_finish(hpn_ctx *c, hpn_rfastqc_result *res)
         HPN_HIP(c, launch_rqc_sizes(u->s.m[k].desc.p, n, (uint32_t)k, (uint32_t *)u->ssz[k].p, (uint32_t *)u->qsz[k].p, (uint32_t *)u->out[k][kLength].p,
                                     info, c->stream));
         if (!n) continue;   // (mate 2 without a record: refused below)
-        if ((rc = scan_sizes(c, u->s, u->status, u->ssz[k], u->soff[k], n, &stotal[k])) != HPN_OK ||
-            (rc = scan_sizes(c, u->s, u->status, u->qsz[k], u->qoff[k], n, &qtotal[k])) != HPN_OK)
+        if ((rc = scan_sizes(c, u->s.info, u->status, u->ssz[k], u->soff[k], n, &stotal[k])) != HPN_OK ||
+            (rc = scan_sizes(c, u->s.info, u->status, u->qsz[k], u->qoff[k], n, &qtotal[k])) != HPN_OK)
             return rc;
     }
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
-    if (u->s.h_info[kRqBad] < short_key) {
-        const uint32_t bad = u->s.h_info[kRqBad];
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
+    if (u->s.info.h[kRqBad] < short_key) {
+        const uint32_t bad = u->s.info.h[kRqBad];
         SortDesc d;
         HPN_HIP(c, hipMemcpy(&d, (const uint8_t *)u->s.m[bad & 1u].desc.p + (size_t)(bad >> 1) * kSortDescBytes, kSortDescBytes, hipMemcpyDeviceToHost));
         return refuse(c, u, res, bad, d.slen < 1u || d.slen > kRqcMaxLen ? HPN_RFASTQC_BAD_LENGTH : HPN_RFASTQC_BAD_QUALITY);
     }
-    const bool ragged = u->s.h_info[kRqRagged] != 0;
+    const bool ragged = u->s.info.h[kRqRagged] != 0;
 
     // ---- the lines gathered, the bytes' domain on the way; matrices and GC per mate
     uint64_t most_s = stotal[0] > stotal[1] ? stotal[0] : stotal[1], most_q = qtotal[0] > qtotal[1] ? qtotal[0] : qtotal[1];
@@ -246,8 +236,8 @@ int hpn_rfastqc_finish(hpn_ctx *c, hpn_rfastqc_result *res)
     }
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
     c->ev_valid[kFamTrim] = true;
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
-    const uint32_t bad = u->s.h_info[kRqBad] < short_key ? u->s.h_info[kRqBad] : short_key;
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
+    const uint32_t bad = u->s.info.h[kRqBad] < short_key ? u->s.info.h[kRqBad] : short_key;
     if (bad != 0xffffffffu) return refuse(c, u, res, bad, bad == short_key ? HPN_RFASTQC_MATE_SHORT : HPN_RFASTQC_BAD_BYTE);
     if (tally_bad[0] || tally_bad[1]) {
         drop_session(u);
@@ -268,17 +258,17 @@ int hpn_rfastqc_finish(hpn_ctx *c, hpn_rfastqc_result *res)
     HPN_HIP(c, launch_rqc_key(t0, d0, t1, d1, u->paired, N, mask, hash, order, klen, c->n_cu, c->stream));
     if ((rc = rq_sort(c, u, hash, order, N, u->hash_bits ? (int)u->hash_bits : 64)) != HPN_OK) return rc;
     HPN_HIP(c, launch_rqc_flags(t0, d0, t1, d1, u->paired, hash, order, klen, N, flag, info, c->n_cu, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
-    res->hash_clashes = u->s.h_info[kRqClash];
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
+    res->hash_clashes = u->s.info.h[kRqClash];
     if (res->hash_clashes) {
         if ((rc = order_clashing_runs(c, u, N)) != HPN_OK) return rc;
         HPN_HIP(c, launch_rqc_flags(t0, d0, t1, d1, u->paired, hash, order, klen, N, flag, info, c->n_cu, c->stream));
     }
     if ((rc = need(c, u->status, uniq_scan_tiles(N) * 8)) != HPN_OK) return rc;
-    HPN_HIP(c, uniq_scan32(flag, gid, N, (u64 *)u->status.p, u->s.ticket(), u->s.err(), c->stream));
+    HPN_HIP(c, uniq_scan32(flag, gid, N, (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(), c->stream));
     uint32_t U = 0;
     HPN_HIP(c, hipMemcpyAsync(&U, gid + N, 4, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
     if ((rc = need(c, u->start, ((size_t)U + 1) * 4)) != HPN_OK || (rc = need(c, u->key, (size_t)U * 8)) != HPN_OK ||
         (rc = need(c, u->out[0][kDup], (size_t)U * 4)) != HPN_OK)
         return rc;
@@ -287,7 +277,7 @@ int hpn_rfastqc_finish(hpn_ctx *c, hpn_rfastqc_result *res)
     if ((rc = rq_sort(c, u, (uint64_t *)u->key.p, dup, U, 32 - __builtin_clz(N))) != HPN_OK) return rc;   // keys are N - count < N
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTally], c->stream));
     c->ev_valid[kFamTally] = true;
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
     finished(U);
     return HPN_OK;
 }
@@ -295,7 +285,7 @@ int hpn_rfastqc_finish(hpn_ctx *c, hpn_rfastqc_result *res)
 int hpn_rfastqc_read(hpn_ctx *c, int which, int mate, uint64_t first_elem, void *out, uint64_t cap_elems, uint64_t *got)
 {
     if (!c || !got) return HPN_E_ARG;
-    hpn_rfastqc_state *u = c->rq;
+    hpn_rfastqc_state *u = state<hpn_rfastqc_state>(c);
     const int rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_rfastqc", got);
     if (rc != HPN_OK) return rc;
     if (which < kDup || which > kLength) return fail(c, HPN_E_ARG, "array %d (0 dup, 1 gc, 2 quality, 3 nucleotide, 4 length)", which);

@@ -7,7 +7,7 @@
 // next 8 bytes and then by run number -- both sorts stable, both over the digits in which two keys differ and no others -- so
 // that the i-th sorted element goes to the i-th tied position.  A run whose neighbours are all equal behind the bytes sorted
 // so far is settled: duplicates leave after one look, and so does every run whose bytes are used up.
-#include "hpn_store.hpp"
+#include "hpn_sorter.hpp"
 #include "kernels/sort_desc.hpp"
 
 namespace hpn {
@@ -44,13 +44,15 @@ constexpr uint32_t kMaxRoundsKseq = 8194;                               // 6 + 8
 enum { kSiBits = kInfoOwn };   // the family's words of the info block: two uint64
 }  // namespace
 
-struct hpn_sort_state {
-    StoreSession s;
-    int by_name = 0, bytes_only = 0;   // bytes_only: the third key mode (hpn_kseq_*), the sequence without its length in front
-    Scratch order, key, val, key_tmp, val_tmp, hist, offs, status, word1, val1, word, head, gid, stay, keep, at, size, off, out;
-    Scratch t_pos[2], t_ord[2], t_len[2], t_run[2], t_kp[2];
-    uint32_t N = 0;
+struct hpn_sort_work {   // what a new session must not inherit
+    Scratch size, off, out;
     uint64_t out_total = 0;
+};
+
+struct hpn_sort_state : FamilyState, hpn_sort_work {
+    static constexpr int kSlot = kStSort;
+    StoreSession s;
+    Sorter sorter;
 };
 
 namespace {
@@ -58,24 +60,19 @@ namespace {
 void drop_session(hpn_sort_state *u)
 {
     session_drop(u->s);
-    Scratch *ss[] = {&u->order, &u->key, &u->val, &u->key_tmp, &u->val_tmp, &u->hist, &u->offs, &u->status, &u->word1, &u->val1, &u->word,
-                     &u->head, &u->gid, &u->stay, &u->keep, &u->at, &u->size, &u->off, &u->out};
-    for (Scratch *s : ss) release_scratch(*s);
-    for (int k = 0; k < 2; ++k) {
-        release_scratch(u->t_pos[k]), release_scratch(u->t_ord[k]), release_scratch(u->t_len[k]);
-        release_scratch(u->t_run[k]), release_scratch(u->t_kp[k]);
-    }
+    static_cast<hpn_sort_work &>(*u) = hpn_sort_work();
+    u->sorter.drop();
 }
 
 // Stable sort of (key, val) by the digits in which two of the n keys differ, interior constant digits left out as well.
-int sort_differing(hpn_ctx *c, hpn_sort_state *u, uint32_t n)
+int sort_differing(hpn_ctx *c, Sorter *u, uint32_t n)
 {
     int rc;
-    uint64_t *bits = (uint64_t *)(u->s.d_info + kSiBits);
+    uint64_t *bits = (uint64_t *)(u->info.d + kSiBits);
     HPN_HIP(c, launch_sort_bits((const uint64_t *)u->key.p, n, bits, c->n_cu, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->info.fetch(c)) != HPN_OK) return rc;
     uint64_t h[2];
-    memcpy(h, u->s.h_info + kSiBits, sizeof h);
+    memcpy(h, u->info.h + kSiBits, sizeof h);
     const uint64_t differ = n ? h[0] ^ h[1] : 0;
     uint32_t digits = 0;
     for (int d = 0; d < 8; ++d)
@@ -87,24 +84,24 @@ int sort_differing(hpn_ctx *c, hpn_sort_state *u, uint32_t n)
         (rc = need(c, u->status, uniq_scan_tiles(hw > n ? hw : n) * 8)) != HPN_OK)
         return rc;
     HPN_HIP(c, uniq_sort_pairs_digits((uint64_t *)u->key.p, (uint32_t *)u->val.p, n, digits, (uint64_t *)u->key_tmp.p, (uint32_t *)u->val_tmp.p,
-                                      (uint32_t *)u->hist.p, (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.ticket(), u->s.err(),
+                                      (uint32_t *)u->hist.p, (uint32_t *)u->offs.p, (u64 *)u->status.p, u->info.ticket(), u->info.err(),
                                       c->stream));
     return HPN_OK;
 }
 
-SortTied tied(hpn_sort_state *u, int k)
+SortTied tied(Sorter *u, int k)
 {
     return SortTied{(uint32_t *)u->t_pos[k].p, (uint32_t *)u->t_ord[k].p, (uint32_t *)u->t_len[k].p, (uint32_t *)u->t_run[k].p, (u64 *)u->t_kp[k].p};
 }
 
 // The runs of the m tied records of side `cur` whose words (the ones just sorted by) are in `word`: settles what is decided
 // behind `c` key bytes and compacts the rest into the other side.  *left: how many stay.
-int settle(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, int cur, const uint64_t *word, uint32_t consumed, uint32_t m, uint32_t *left)
+int settle(hpn_ctx *c, Sorter *u, const uint8_t *text, int cur, const uint64_t *word, uint32_t consumed, uint32_t m, uint32_t *left)
 {
     int rc;
     if ((rc = need(c, u->status, uniq_scan_tiles(m) * 8)) != HPN_OK) return rc;
     uint32_t *head = (uint32_t *)u->head.p, *gid = (uint32_t *)u->gid.p, *stay = (uint32_t *)u->stay.p, *keep = (uint32_t *)u->keep.p;
-    uint32_t *at = (uint32_t *)u->at.p, *ticket = u->s.ticket(), *err = u->s.err();
+    uint32_t *at = (uint32_t *)u->at.p, *ticket = u->info.ticket(), *err = u->info.err();
     const SortTied a = tied(u, cur), b = tied(u, cur ^ 1);
     HPN_HIP(c, launch_sort_heads(word, a.run, m, head, c->stream));
     HPN_HIP(c, uniq_scan32(head, gid, m, (u64 *)u->status.p, ticket, err, c->stream));
@@ -112,18 +109,19 @@ int settle(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, int cur, const ui
     HPN_HIP(c, uniq_scan32(keep, at, m, (u64 *)u->status.p, ticket, err, c->stream));
     uint32_t n_left = 0;
     HPN_HIP(c, hipMemcpyAsync(&n_left, at + m, 4, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->info.fetch(c)) != HPN_OK) return rc;
     if (n_left) HPN_HIP(c, launch_sort_compact(keep, at, head, gid, a, m, b, c->stream));
     *left = n_left;
     return HPN_OK;
 }
 
-// the N records that `desc` describes in `text`, by the state's key mode, into u->order (the info block is u->s's)
-int order_records(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, const void *desc, hpn_sort_result *res)
+}  // namespace
+
+int hpn::order_records(hpn_ctx *c, Sorter *u, const uint8_t *text, const void *desc, uint32_t N, hpn_sort_result *res)
 {
     int rc;
-    const uint32_t N = u->N;
     const uint32_t max_rounds = u->bytes_only ? kMaxRoundsKseq : kMaxRounds;
+    if ((rc = u->info.alloc(c)) != HPN_OK || (rc = u->info.zero(c)) != HPN_OK) return rc;
     if ((rc = need(c, u->order, (size_t)N * 4)) != HPN_OK) return rc;
     if (!N) return HPN_OK;
     Scratch *per4[] = {&u->val, &u->val1, &u->head, &u->stay, &u->keep, &u->t_pos[0], &u->t_pos[1], &u->t_ord[0], &u->t_ord[1],
@@ -163,81 +161,33 @@ int order_records(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, const void
     return HPN_OK;
 }
 
-}  // namespace
-
-namespace hpn {
-// The refinement sort for a session of another family (hpn_kseq.hip), by the sequence's bytes alone: a sort state of its own
-// (its arrays and its info block, no store), the order of the n records of `desc` in `text`, and the order's array.
-hpn_sort_state *sort_state_new(hpn_ctx *c)
-{
-    hpn_sort_state *u = new hpn_sort_state;
-    u->bytes_only = 1;
-    if (info_alloc(c, u->s) != HPN_OK) {
-        info_free(u->s);
-        delete u;
-        return nullptr;
-    }
-    return u;
-}
-
-void sort_state_drop(hpn_sort_state *u) { drop_session(u); }
-
-void sort_state_free(hpn_sort_state *u)
-{
-    if (!u) return;
-    drop_session(u);
-    info_free(u->s);
-    delete u;
-}
-
-int sort_state_order(hpn_ctx *c, hpn_sort_state *u, const uint8_t *text, const void *desc, uint32_t n, uint32_t *rounds, uint64_t *refined,
-                     const uint32_t **d_order)
-{
-    hpn_sort_result res = {};
-    u->N = n;
-    HPN_HIP(c, hipMemsetAsync(u->s.d_info, 0, kInfoWords * sizeof(uint32_t), c->stream));
-    const int rc = order_records(c, u, text, desc, &res);
-    *rounds = res.rounds, *refined = res.refined;
-    *d_order = (const uint32_t *)u->order.p;
-    return rc;
-}
-
-void sort_release(hpn_ctx *c)
-{
-    if (!c->sq) return;
-    drop_session(c->sq);
-    info_free(c->sq->s);
-    delete c->sq;
-    c->sq = nullptr;
-}
-}  // namespace hpn
-
 extern "C" {
 
 int hpn_fastq_sort_begin(hpn_ctx *c, int by_name, uint64_t max_bytes)
 {
     if (!c) return HPN_E_ARG;
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->sq) c->sq = new hpn_sort_state;
-    drop_session(c->sq);
-    c->sq->by_name = by_name ? 1 : 0;
-    return session_begin(c, c->sq->s, 1, max_bytes);
+    hpn_sort_state *u = state_make<hpn_sort_state>(c);
+    drop_session(u);
+    u->sorter.by_name = by_name ? 1 : 0;
+    return session_begin(c, u->s, 1, max_bytes);
 }
 
 int hpn_fastq_sort_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->sq ? &c->sq->s : nullptr, "hpn_fastq_sort", 0, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, false, info);
+    hpn_sort_state *u = state<hpn_sort_state>(c);
+    return session_add(c, u ? &u->s : nullptr, "hpn_fastq_sort", 0, kSortDescBytes, frame_by<launch_sort_frame>, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_fastq_sort_finish(hpn_ctx *c, hpn_sort_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_sort_state *u = c->sq;
+    hpn_sort_state *u = state<hpn_sort_state>(c);
     int rc;
     if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_sort", kSortDescBytes)) != HPN_OK) return rc;
     memset(res, 0, sizeof *res);
-    const uint32_t N = u->N = (uint32_t)u->s.m[0].n;
+    const uint32_t N = (uint32_t)u->s.m[0].n;
     res->n_records = N;
     uint64_t framed = 0;   // where the last record ends (a last line without '\n': behind the byte it lost)
     if (N) {
@@ -247,17 +197,17 @@ int hpn_fastq_sort_finish(hpn_ctx *c, hpn_sort_result *res)
     }
     res->lone_line = framed < u->s.m[0].len ? 1u : 0u;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTally], c->stream));
-    if ((rc = order_records(c, u, u->s.text(0), u->s.m[0].desc.p, res)) != HPN_OK) return rc;
+    if ((rc = order_records(c, &u->sorter, u->s.text(0), u->s.m[0].desc.p, N, res)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTally], c->stream));
     c->ev_valid[kFamTally] = true;
     // the output text
     if ((rc = need(c, u->size, (size_t)N * 4)) != HPN_OK || (rc = need(c, u->off, ((size_t)N + 1) * 8)) != HPN_OK) return rc;
-    HPN_HIP(c, launch_sort_sizes(u->s.m[0].desc.p, (const uint32_t *)u->order.p, N, (uint32_t *)u->size.p, c->stream));
+    HPN_HIP(c, launch_sort_sizes(u->s.m[0].desc.p, (const uint32_t *)u->sorter.order.p, N, (uint32_t *)u->size.p, c->stream));
     uint64_t total = 0;
-    if ((rc = scan_sizes(c, u->s, u->status, u->size, u->off, N, &total)) != HPN_OK) return rc;
+    if ((rc = scan_sizes(c, u->s.info, u->sorter.status, u->size, u->off, N, &total)) != HPN_OK) return rc;
     if ((rc = need(c, u->out, total)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
-    HPN_HIP(c, launch_sort_write(u->s.text(0), u->s.m[0].desc.p, (const uint32_t *)u->order.p, (const uint64_t *)u->off.p, N,
+    HPN_HIP(c, launch_sort_write(u->s.text(0), u->s.m[0].desc.p, (const uint32_t *)u->sorter.order.p, (const uint64_t *)u->off.p, N,
                                  (uint8_t *)u->out.p, c->n_cu, c->stream));
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
     c->ev_valid[kFamTrim] = true;
@@ -270,7 +220,7 @@ int hpn_fastq_sort_finish(hpn_ctx *c, hpn_sort_result *res)
 int hpn_fastq_sort_write(hpn_ctx *c, uint64_t offset, void *out, uint64_t cap, uint64_t *written)
 {
     if (!c || !written) return HPN_E_ARG;
-    hpn_sort_state *u = c->sq;
+    hpn_sort_state *u = state<hpn_sort_state>(c);
     const int rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_sort", written);
     return rc != HPN_OK ? rc : session_write_slice(c, u->out, u->out_total, offset, out, cap, written);
 }

@@ -30,7 +30,8 @@ constexpr uint32_t kNoKey = 0xfffffffeu;
 typedef hpn_stored_span StoredSpec;      // (kernels/bam_split.hip reads the same layout)
 }  // namespace
 
-struct hpn_split_state {
+struct hpn_split_state : FamilyState {
+    static constexpr int kSlot = kStSplit;
     bool open = false, dead = false, ended = false;
     int32_t n_ref = 0;
     bool level0 = false;
@@ -46,28 +47,13 @@ struct hpn_split_state {
     uint64_t payload_bytes = 0, stored_bytes = 0;
 };
 
-namespace hpn {
-void split_release(hpn_ctx *c)
-{
-    hpn_split_state *u = c->sp;
-    if (!u) return;
-    Scratch *ss[] = {&u->Q, &u->key, &u->ja, &u->jb, &u->jc, &u->mark, &u->tiles, &u->blocks, &u->pay, &u->img, &u->keep, &u->specs, &u->counts,
-                     &u->state, &u->info};
-    for (Scratch *s : ss)
-        if (s->p) (void)hipFree(s->p);
-    delete u;
-    c->sp = nullptr;
-}
-}  // namespace hpn
-
 extern "C" {
 
 int hpn_bam_split_begin(hpn_ctx *c, int32_t n_ref, int level0)
 {
     if (!c || n_ref < 0) return HPN_E_ARG;
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->sp) c->sp = new hpn_split_state;
-    hpn_split_state *u = c->sp;
+    hpn_split_state *u = state_make<hpn_split_state>(c);
     int rc;
     if ((rc = scratch_reserve(c, u->counts, ((size_t)n_ref + 1) * sizeof(u64))) != HPN_OK) return rc;
     if ((rc = scratch_reserve(c, u->state, 64)) != HPN_OK || (rc = scratch_reserve(c, u->info, 64)) != HPN_OK) return rc;
@@ -91,7 +77,7 @@ static void split_report(const hpn_split_state *u, hpn_split_info *info)
 int hpn_bam_split_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, int last, hpn_split_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_split_state *u = c->sp;
+    hpn_split_state *u = state<hpn_split_state>(c);
     if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_add_raw_dev before hpn_bam_split_begin");
     if (u->ended) return fail(c, HPN_E_STATE, "hpn_bam_split_add_raw_dev behind the call that ended the file");
     HPN_HIP(c, hipSetDevice(c->device));
@@ -202,8 +188,7 @@ int hpn_bgzf_stored_dev(hpn_ctx *c, const uint8_t *d_data, const hpn_stored_span
         if (spans[k].len == 0 || spans[k].len > kFull) return fail(c, HPN_E_ARG, "hpn_bgzf_stored_dev: span %u has %u bytes", k, spans[k].len);
     if (!n_spans) return HPN_OK;
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->sp) c->sp = new hpn_split_state;
-    hpn_split_state *u = c->sp;
+    hpn_split_state *u = state_make<hpn_split_state>(c);
     const int rc = scratch_reserve(c, u->specs, (size_t)n_spans * sizeof(StoredSpec));
     if (rc != HPN_OK) return rc;
     HPN_HIP(c, hipMemcpyAsync(u->specs.p, spans, (size_t)n_spans * sizeof(StoredSpec), hipMemcpyHostToDevice, c->stream));
@@ -215,7 +200,7 @@ int hpn_bgzf_stored_dev(hpn_ctx *c, const uint8_t *d_data, const hpn_stored_span
 int hpn_bam_split_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
 {
     if (!c || !n) return HPN_E_ARG;
-    hpn_split_state *u = c->sp;
+    hpn_split_state *u = state<hpn_split_state>(c);
     if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_blocks before hpn_bam_split_begin");
     const uint64_t have = u->list.size();
     if (first > have) return fail(c, HPN_E_ARG, "block %llu of %llu", (unsigned long long)first, (unsigned long long)have);
@@ -229,7 +214,7 @@ int hpn_bam_split_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint6
 int hpn_bam_split_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n_bytes)
 {
     if (!c || !d_payload || !n_bytes) return HPN_E_ARG;
-    hpn_split_state *u = c->sp;
+    hpn_split_state *u = state<hpn_split_state>(c);
     if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_payload_dev before hpn_bam_split_begin");
     *d_payload = (const uint8_t *)u->pay.p, *n_bytes = u->payload_bytes;
     return HPN_OK;
@@ -238,7 +223,7 @@ int hpn_bam_split_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n
 int hpn_bam_split_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_bytes)
 {
     if (!c || !d_image || !n_bytes) return HPN_E_ARG;
-    hpn_split_state *u = c->sp;
+    hpn_split_state *u = state<hpn_split_state>(c);
     if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_stored_dev before hpn_bam_split_begin");
     if (!u->level0) return fail(c, HPN_E_STATE, "hpn_bam_split_stored_dev: the session was not begun with level0");
     *d_image = (const uint8_t *)u->img.p, *n_bytes = u->stored_bytes;
@@ -248,7 +233,7 @@ int hpn_bam_split_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_by
 int hpn_bam_split_finish(hpn_ctx *c, hpn_split_result *res, uint64_t *counts)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_split_state *u = c->sp;
+    hpn_split_state *u = state<hpn_split_state>(c);
     if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_finish before hpn_bam_split_begin");
     if (!u->dead && u->fill) return fail(c, HPN_E_STATE, "hpn_bam_split_finish with a block open: the last hpn_bam_split_add_raw_dev takes last = 1");
     HPN_HIP(c, hipSetDevice(c->device));

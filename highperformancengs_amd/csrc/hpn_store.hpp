@@ -1,11 +1,15 @@
 // hpn_store.hpp -- the device store behind the nine store-backed entry points (hpn_fastq_uniq_*, _uniqq_*, _usort_*, _sort_*, _pair_*,
 // hpn_twobit_pack_*, hpn_mrle_*, hpn_rfastqc_*, hpn_kseq_*) and the session around it.  The store: a stream's bytes are appended as they come and framed WHERE THEY
 // LIE (no carry is copied: the next chunk's framing starts at the first unfinished record), one descriptor per record.  What a
-// descriptor holds is the caller's: it hands in the kernel that writes them (kernels/fastq_uniq.hip: k_uniq_keys,
-// kernels/fastq_sort.hip: k_sort_frame) behind the line index of kernels/fastq_text.hip.  The session: one or two stores under
-// one byte limit, the _begin / _add / _finish / _write life cycle and its messages, and the info block the scans report through.
+// descriptor holds is the caller's: it hands in the hook that writes them (frame_by<> over kernels/fastq_uniq.hip: k_uniq_keys
+// or kernels/fastq_sort.hip: k_sort_frame; hpn_kseq.hip: kseq_frame) behind the line index of kernels/fastq_text.hip.  The
+// session: one or two stores under one byte limit, the _begin / _add / _finish / _write life cycle and its messages, and the
+// info block the scans report through.  Every buffer here owns what it holds (Scratch, InfoBlock): a state that goes frees them,
+// and a family drops a session by assigning a fresh value to what a new session must not inherit.
 #pragma once
 #include <string.h>
+
+#include <utility>
 
 #include "hpn_ctx.hpp"
 
@@ -40,22 +44,30 @@ struct RecordStore {
     bool closed = false;
 };
 
-// writes the descriptors of the records that the line index d_nl holds (launched over an upper bound of records); `user` is
-// the caller's own (the kernels of the gzgets families take none: nullptr)
-typedef hipError_t (*store_frame_fn)(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
-                                     void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *user);
+// The frame hook: writes the descriptors of the records that the line index d_nl holds (run over an upper bound of records) on
+// the context's stream, and returns an HPN status with its message set; a hook that fails closes the session.  `user` is the
+// caller's own (the kernels of the gzgets families take none: nullptr).
+struct FrameArgs {
+    const uint8_t *d_slot;
+    const uint32_t *d_nl;
+    uint32_t begin, end;
+    int last;
+    uint64_t origin;
+    void *d_desc;
+    uint32_t max_records;
+    uint32_t *d_state;
+    void *user;
+};
+typedef int (*store_frame_fn)(hpn_ctx *c, const FrameArgs &a);
 
-inline void release_scratch(Scratch &s)
+// the hook over a plain launcher (launch_sort_frame, launch_uniq_keys, launch_uniqq_keys)
+typedef hipError_t (*frame_launch_fn)(const uint8_t *d_slot, const uint32_t *d_nl, uint32_t begin, uint32_t end, int last, uint64_t origin,
+                                      void *d_desc, uint32_t max_records, uint32_t *d_state, hipStream_t st, void *user);
+template <frame_launch_fn launch>
+int frame_by(hpn_ctx *c, const FrameArgs &a)
 {
-    if (s.p) (void)hipFree(s.p);
-    s.p = nullptr, s.cap = 0;
-}
-
-inline void store_release(RecordStore &m)
-{
-    release_scratch(m.store);
-    release_scratch(m.desc);
-    m.len = m.pos = m.n = 0, m.closed = false;
+    HPN_HIP(c, launch(a.d_slot, a.d_nl, a.begin, a.end, a.last, a.origin, a.d_desc, a.max_records, a.d_state, c->stream, a.user));
+    return HPN_OK;
 }
 
 // a buffer that keeps its first `keep` bytes when it grows (doubling: the copies add up to less than one more pass)
@@ -64,18 +76,19 @@ inline int grow_keep(hpn_ctx *c, Scratch &s, size_t bytes, size_t keep)
     if (bytes <= s.cap) return HPN_OK;
     size_t want = s.cap * 2 > bytes ? s.cap * 2 : bytes;
     if (want < ((size_t)1 << 20)) want = (size_t)1 << 20;
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, want);
+    Scratch grown;   // (a copy that fails frees it and leaves `s` as it was)
+    hipError_t e = hipMalloc(&grown.p, want);
     if (e != hipSuccess) {
         (void)hipGetLastError();
+        grown.p = nullptr;
         return fail(c, HPN_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
     }
+    grown.cap = want;
     if (s.p) {
-        if (keep) HPN_HIP(c, hipMemcpyAsync(p, s.p, keep, hipMemcpyDeviceToDevice, c->stream));
+        if (keep) HPN_HIP(c, hipMemcpyAsync(grown.p, s.p, keep, hipMemcpyDeviceToDevice, c->stream));
         HPN_HIP(c, hipStreamSynchronize(c->stream));
-        HPN_HIP(c, hipFree(s.p));
     }
-    s.p = p, s.cap = want;
+    s = std::move(grown);
     return HPN_OK;
 }
 
@@ -136,8 +149,12 @@ inline int store_add(hpn_ctx *c, RecordStore &m, size_t desc_bytes, store_frame_
         return fail(c, HPN_E_DOMAIN, "2^31 or more records");
     }
     if ((rc = grow_keep(c, m.desc, (size_t)(m.n + max_records + 1) * desc_bytes, (size_t)m.n * desc_bytes)) != HPN_OK) return rc;
-    HPN_HIP(c, frame(slot, (const uint32_t *)c->t_nl.p, begin, end, last, m.pos, (uint8_t *)m.desc.p + (size_t)m.n * desc_bytes, max_records,
-                     c->t_state, c->stream, user));
+    const FrameArgs fa = {slot, (const uint32_t *)c->t_nl.p, begin, end, last, m.pos, (uint8_t *)m.desc.p + (size_t)m.n * desc_bytes, max_records,
+                          c->t_state, user};
+    if ((rc = frame(c, fa)) != HPN_OK) {   // the chunk is stored but not framed
+        *close = true;
+        return rc;
+    }
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamText], c->stream));
     c->ev_valid[kFamText] = true;
     HPN_HIP(c, hipMemcpyAsync(c->h_tstate, c->t_state, kStateWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -158,52 +175,68 @@ inline int store_add(hpn_ctx *c, RecordStore &m, size_t desc_bytes, store_frame_
 // The device's info block (uint32 words): the scans' and sorts' hand-off ticket and error flag, then the family's own words.
 enum { kInfoTicket = 0, kInfoErr = 1, kInfoOwn = 2, kInfoWords = 16 };
 
+struct InfoBlock {
+    uint32_t *d = nullptr, *h = nullptr;   // kInfoWords each; h: the pinned mirror
+    InfoBlock() = default;
+    InfoBlock(InfoBlock &&o) noexcept : d(o.d), h(o.h) { o.d = o.h = nullptr; }
+    InfoBlock &operator=(InfoBlock &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            d = o.d, h = o.h;
+            o.d = o.h = nullptr;
+        }
+        return *this;
+    }
+    ~InfoBlock() { release(); }
+    void release()
+    {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        d = h = nullptr;
+    }
+    uint32_t *ticket() const { return d + kInfoTicket; }
+    uint32_t *err() const { return d + kInfoErr; }
+    int alloc(hpn_ctx *c)   // on first use
+    {
+        if (!d) HPN_HIP(c, hipMalloc((void **)&d, kInfoWords * sizeof(uint32_t)));
+        if (!h) HPN_HIP(c, hipHostMalloc((void **)&h, kInfoWords * sizeof(uint32_t), hipHostMallocDefault));
+        return HPN_OK;
+    }
+    int zero(hpn_ctx *c)
+    {
+        HPN_HIP(c, hipMemsetAsync(d, 0, kInfoWords * sizeof(uint32_t), c->stream));
+        return HPN_OK;
+    }
+    int fetch(hpn_ctx *c)   // the block on the host; waits for the stream
+    {
+        HPN_HIP(c, hipMemcpyAsync(h, d, kInfoWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HPN_HIP(c, hipStreamSynchronize(c->stream));
+        if (h[kInfoErr]) return fail(c, HPN_E_HIP, "prefix-scan hand-off timed out");
+        return HPN_OK;
+    }
+};
+
 struct StoreSession {
     int n_streams = 1;
     RecordStore m[2];
     uint64_t limit = 0;
     bool open = false, finished = false;
-    uint32_t *d_info = nullptr, *h_info = nullptr;   // kInfoWords each; h_info: the pinned mirror
-    uint32_t *ticket() const { return d_info + kInfoTicket; }
-    uint32_t *err() const { return d_info + kInfoErr; }
+    InfoBlock info;
     const uint8_t *text(int k) const { return (const uint8_t *)m[k].store.p + kStorePad; }
 };
 
-inline int info_alloc(hpn_ctx *c, StoreSession &s)
-{
-    if (!s.d_info) {
-        HPN_HIP(c, hipMalloc((void **)&s.d_info, kInfoWords * sizeof(uint32_t)));
-        HPN_HIP(c, hipHostMalloc((void **)&s.h_info, kInfoWords * sizeof(uint32_t), hipHostMallocDefault));
-    }
-    return HPN_OK;
-}
-
-inline void info_free(StoreSession &s)
-{
-    if (s.d_info) (void)hipFree(s.d_info);
-    if (s.h_info) (void)hipHostFree(s.h_info);
-    s.d_info = s.h_info = nullptr;
-}
-
-// the info block on the host; waits for the stream
-inline int info_fetch(hpn_ctx *c, StoreSession &s)
-{
-    HPN_HIP(c, hipMemcpyAsync(s.h_info, s.d_info, kInfoWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (s.h_info[kInfoErr]) return fail(c, HPN_E_HIP, "prefix-scan hand-off timed out");
-    return HPN_OK;
-}
-
+// the stores go, the info block stays
 inline void session_drop(StoreSession &s)
 {
-    for (RecordStore &m : s.m) store_release(m);
+    for (RecordStore &m : s.m) m = RecordStore();
     s.open = s.finished = false;
 }
 
 // _begin, behind the family's own drop: the info block on first use, the limit, open
 inline int session_begin(hpn_ctx *c, StoreSession &s, int n_streams, uint64_t max_bytes)
 {
-    const int rc = info_alloc(c, s);
+    const int rc = s.info.alloc(c);
     if (rc != HPN_OK) return rc;
     session_drop(s);
     if (!max_bytes) {   // half of what is free: the other half is the reserve for the store's growth, the sorts' arrays and the output
@@ -256,18 +289,17 @@ inline int session_finish_begin(hpn_ctx *c, StoreSession *s, const char *api, si
     int rc;
     for (int k = 0; k < s->n_streams; ++k)
         if ((rc = grow_keep(c, s->m[k].store, 2 * kStorePad, 0)) != HPN_OK || (rc = grow_keep(c, s->m[k].desc, desc_bytes, 0)) != HPN_OK) return rc;
-    HPN_HIP(c, hipMemsetAsync(s->d_info, 0, kInfoWords * sizeof(uint32_t), c->stream));
-    return HPN_OK;
+    return s->info.zero(c);
 }
 
 // n 32-bit sizes -> n + 1 64-bit offsets; *total: the last one, on the host
-inline int scan_sizes(hpn_ctx *c, StoreSession &s, Scratch &status, const Scratch &size, const Scratch &off, uint64_t n, uint64_t *total)
+inline int scan_sizes(hpn_ctx *c, InfoBlock &info, Scratch &status, const Scratch &size, const Scratch &off, uint64_t n, uint64_t *total)
 {
     int rc;
     if ((rc = need(c, status, uniq_scan_tiles(n) * 8)) != HPN_OK) return rc;
-    HPN_HIP(c, uniq_scan64((const uint32_t *)size.p, (uint64_t *)off.p, n, (u64 *)status.p, s.ticket(), s.err(), c->stream));
+    HPN_HIP(c, uniq_scan64((const uint32_t *)size.p, (uint64_t *)off.p, n, (u64 *)status.p, info.ticket(), info.err(), c->stream));
     HPN_HIP(c, hipMemcpyAsync(total, (const uint64_t *)off.p + n, 8, hipMemcpyDeviceToHost, c->stream));
-    return info_fetch(c, s);
+    return info.fetch(c);
 }
 
 // What every _write opens with, and its slice copy: up to `cap` bytes of the `total` that lie in `out`, from `offset` on

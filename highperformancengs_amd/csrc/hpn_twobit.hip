@@ -24,10 +24,14 @@ namespace {
 enum { kTbBad = kInfoOwn };   // the family's word of the info block
 }  // namespace
 
-struct hpn_twobit_state {
-    StoreSession s;
+struct hpn_twobit_work {   // what a new session must not inherit
     Scratch size, off, status, out;
     uint64_t out_total = 0;
+};
+
+struct hpn_twobit_state : FamilyState, hpn_twobit_work {
+    static constexpr int kSlot = kStTwobit;
+    StoreSession s;
 };
 
 namespace {
@@ -35,23 +39,10 @@ namespace {
 void drop_session(hpn_twobit_state *u)
 {
     session_drop(u->s);
-    Scratch *ss[] = {&u->size, &u->off, &u->status, &u->out};
-    for (Scratch *s : ss) release_scratch(*s);
-    u->out_total = 0;
+    static_cast<hpn_twobit_work &>(*u) = hpn_twobit_work();
 }
 
 }  // namespace
-
-namespace hpn {
-void twobit_release(hpn_ctx *c)
-{
-    if (!c->tb) return;
-    drop_session(c->tb);
-    info_free(c->tb->s);
-    delete c->tb;
-    c->tb = nullptr;
-}
-}  // namespace hpn
 
 extern "C" {
 
@@ -59,21 +50,22 @@ int hpn_twobit_pack_begin(hpn_ctx *c, uint64_t max_bytes)
 {
     if (!c) return HPN_E_ARG;
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->tb) c->tb = new hpn_twobit_state;
-    drop_session(c->tb);
-    return session_begin(c, c->tb->s, 1, max_bytes);
+    hpn_twobit_state *u = state_make<hpn_twobit_state>(c);
+    drop_session(u);
+    return session_begin(c, u->s, 1, max_bytes);
 }
 
 int hpn_twobit_pack_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_sort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->tb ? &c->tb->s : nullptr, "hpn_twobit_pack", 0, kSortDescBytes, launch_sort_frame, nullptr, 4u, text, nbytes, last, false, info);
+    hpn_twobit_state *u = state<hpn_twobit_state>(c);
+    return session_add(c, u ? &u->s : nullptr, "hpn_twobit_pack", 0, kSortDescBytes, frame_by<launch_sort_frame>, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_twobit_pack_finish(hpn_ctx *c, hpn_twobit_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_twobit_state *u = c->tb;
+    hpn_twobit_state *u = state<hpn_twobit_state>(c);
     int rc;
     if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_twobit_pack", kSortDescBytes)) != HPN_OK) return rc;
     memset(res, 0, sizeof *res);
@@ -93,19 +85,19 @@ int hpn_twobit_pack_finish(hpn_ctx *c, hpn_twobit_result *res)
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
     HPN_HIP(c, launch_pack_sizes(u->s.m[0].desc.p, N, (uint32_t *)u->size.p, c->stream));
     uint64_t sum = 0;
-    if ((rc = scan_sizes(c, u->s, u->status, u->size, u->off, N, &sum)) != HPN_OK) return rc;
+    if ((rc = scan_sizes(c, u->s.info, u->status, u->size, u->off, N, &sum)) != HPN_OK) return rc;
     const uint64_t total = 2u + sum;
     if ((rc = need(c, u->out, total)) != HPN_OK) return rc;
-    HPN_HIP(c, launch_pack_write(u->s.text(0), u->s.m[0].desc.p, (const uint64_t *)u->off.p, N, (uint8_t *)u->out.p, u->s.d_info + kTbBad, c->n_cu,
+    HPN_HIP(c, launch_pack_write(u->s.text(0), u->s.m[0].desc.p, (const uint64_t *)u->off.p, N, (uint8_t *)u->out.p, u->s.info.d + kTbBad, c->n_cu,
                                  c->stream));
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
     c->ev_valid[kFamTrim] = true;
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
-    if (u->s.h_info[kTbBad] != 0xffffffffu) {
-        res->bad_record = (int64_t)u->s.h_info[kTbBad];
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
+    if (u->s.info.h[kTbBad] != 0xffffffffu) {
+        res->bad_record = (int64_t)u->s.info.h[kTbBad];
         drop_session(u);
         return fail(c, HPN_E_DOMAIN, "record %u (0-based) has a sequence byte of 0x80 or more: the reference indexes its table with a signed char there",
-                    u->s.h_info[kTbBad]);
+                    u->s.info.h[kTbBad]);
     }
     u->out_total = res->out_bytes = total;
     u->s.finished = true;
@@ -115,7 +107,7 @@ int hpn_twobit_pack_finish(hpn_ctx *c, hpn_twobit_result *res)
 int hpn_twobit_pack_write(hpn_ctx *c, uint64_t offset, void *out, uint64_t cap, uint64_t *written)
 {
     if (!c || !written) return HPN_E_ARG;
-    hpn_twobit_state *u = c->tb;
+    hpn_twobit_state *u = state<hpn_twobit_state>(c);
     const int rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_twobit_pack", written);
     return rc != HPN_OK ? rc : session_write_slice(c, u->out, u->out_total, offset, out, cap, written);
 }

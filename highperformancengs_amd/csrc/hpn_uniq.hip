@@ -20,7 +20,7 @@ int build_output(hpn_ctx *c, hpn_uniq_state *u, int which, int mate)
     if ((rc = need(c, u->size, (size_t)U * 4)) != HPN_OK || (rc = need(c, u->off, ((size_t)U + 1) * 8)) != HPN_OK) return rc;
     HPN_HIP(c, launch_uniq_sizes(u->s.m[mate].desc.p, list, (const uint32_t *)u->rep.p, (const uint32_t *)u->count.p, U, (uint32_t *)u->size.p, c->stream));
     uint64_t total = 0;
-    if ((rc = scan_sizes(c, u->s, u->status, u->size, u->off, U, &total)) != HPN_OK) return rc;
+    if ((rc = scan_sizes(c, u->s.info, u->status, u->size, u->off, U, &total)) != HPN_OK) return rc;
     u->cached_which = u->cached_mate = -1;
     if ((rc = need(c, u->out, total)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
@@ -35,17 +35,6 @@ int build_output(hpn_ctx *c, hpn_uniq_state *u, int which, int mate)
 
 }  // namespace
 
-namespace hpn {
-void uniq_release(hpn_ctx *c)
-{
-    if (!c->uq) return;
-    uniq_drop_session(c->uq);
-    info_free(c->uq->s);
-    delete c->uq;
-    c->uq = nullptr;
-}
-}  // namespace hpn
-
 extern "C" {
 
 int hpn_fastq_uniq_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t hash_bits)
@@ -53,21 +42,22 @@ int hpn_fastq_uniq_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t ha
     if (!c) return HPN_E_ARG;
     if (hash_bits > 63) return fail(c, HPN_E_ARG, "hash_bits %u (0 = all 64, or 1 .. 63)", hash_bits);
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->uq) c->uq = new hpn_uniq_state;
-    uniq_drop_session(c->uq);
-    return uniq_begin(c, c->uq, paired, max_bytes, hash_bits);
+    hpn_uniq_state *u = state_make<hpn_uniq_state>(c);
+    uniq_drop_session(u);
+    return uniq_begin(c, u, paired, max_bytes, hash_bits);
 }
 
 int hpn_fastq_uniq_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->uq ? &c->uq->s : nullptr, "hpn_fastq_uniq", mate, kUniqDescBytes, launch_uniq_keys, nullptr, 4u, text, nbytes, last, false, info);
+    hpn_uniq_state *u = state<hpn_uniq_state>(c);
+    return session_add(c, u ? &u->s : nullptr, "hpn_fastq_uniq", mate, kUniqDescBytes, frame_by<launch_uniq_keys>, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_fastq_uniq_finish(hpn_ctx *c, hpn_uniq_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_uniq_state *u = c->uq;
+    hpn_uniq_state *u = state<hpn_uniq_state>(c);
     int rc;
     if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_uniq", kUniqDescBytes)) != HPN_OK) return rc;
     memset(res, 0, sizeof *res);
@@ -91,7 +81,7 @@ int hpn_fastq_uniq_finish(hpn_ctx *c, hpn_uniq_result *res)
 int hpn_fastq_uniq_write(hpn_ctx *c, int which, int mate, uint64_t offset, void *out, uint64_t cap, uint64_t *written)
 {
     if (!c || !written) return HPN_E_ARG;
-    hpn_uniq_state *u = c->uq;
+    hpn_uniq_state *u = state<hpn_uniq_state>(c);
     int rc;
     if ((rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_uniq", written)) != HPN_OK) return rc;
     if (which != HPN_UNIQ_TABLE_ORDER && which != HPN_UNIQ_KEY_ORDER) return fail(c, HPN_E_ARG, "unknown output %d", which);
@@ -106,31 +96,22 @@ int hpn_sort_pairs_u64(hpn_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t n)
     if (!c || (n && (!keys || !vals))) return HPN_E_ARG;
     if (n >= (1ull << 31)) return fail(c, HPN_E_DOMAIN, "2^31 or more keys");
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->uq) c->uq = new hpn_uniq_state;
-    hpn_uniq_state *u = c->uq;
-    int rc = info_alloc(c, u->s);
+    hpn_uniq_state *u = state_make<hpn_uniq_state>(c);
+    int rc = u->s.info.alloc(c);
     if (rc != HPN_OK) return rc;
     if (u->s.open && !u->s.finished) return fail(c, HPN_E_STATE, "a hpn_fastq_uniq session is collecting text: its work space is in use");
-    struct Pair {   // the caller's arrays on the device, for this call only
-        Scratch k, v;
-        ~Pair()
-        {
-            release_scratch(k);
-            release_scratch(v);
-        }
-    } d;
-    if ((rc = need(c, d.k, (size_t)n * 8)) != HPN_OK || (rc = need(c, d.v, (size_t)n * 4)) != HPN_OK) return rc;
-    HPN_HIP(c, hipMemsetAsync(u->s.d_info, 0, kInfoWords * sizeof(uint32_t), c->stream));
+    Scratch k, v;   // the caller's arrays on the device, for this call only
+    if ((rc = need(c, k, (size_t)n * 8)) != HPN_OK || (rc = need(c, v, (size_t)n * 4)) != HPN_OK || (rc = u->s.info.zero(c)) != HPN_OK) return rc;
     if (n) {
-        HPN_HIP(c, hipMemcpyAsync(d.k.p, keys, (size_t)n * 8, hipMemcpyDefault, c->stream));
-        HPN_HIP(c, hipMemcpyAsync(d.v.p, vals, (size_t)n * 4, hipMemcpyDefault, c->stream));
+        HPN_HIP(c, hipMemcpyAsync(k.p, keys, (size_t)n * 8, hipMemcpyDefault, c->stream));
+        HPN_HIP(c, hipMemcpyAsync(v.p, vals, (size_t)n * 4, hipMemcpyDefault, c->stream));
     }
-    if ((rc = uniq_sort(c, u, (uint64_t *)d.k.p, (uint32_t *)d.v.p, (uint32_t)n, 0, 64)) != HPN_OK) return rc;
+    if ((rc = uniq_sort(c, u, (uint64_t *)k.p, (uint32_t *)v.p, (uint32_t)n, 0, 64)) != HPN_OK) return rc;
     if (n) {
-        HPN_HIP(c, hipMemcpyAsync(keys, d.k.p, (size_t)n * 8, hipMemcpyDefault, c->stream));
-        HPN_HIP(c, hipMemcpyAsync(vals, d.v.p, (size_t)n * 4, hipMemcpyDefault, c->stream));
+        HPN_HIP(c, hipMemcpyAsync(keys, k.p, (size_t)n * 8, hipMemcpyDefault, c->stream));
+        HPN_HIP(c, hipMemcpyAsync(vals, v.p, (size_t)n * 4, hipMemcpyDefault, c->stream));
     }
-    return info_fetch(c, u->s);   // (waits for the stream: the arrays are free to go)
+    return u->s.info.fetch(c);   // (waits for the stream: the arrays are free to go)
 }
 
 }  // extern "C"

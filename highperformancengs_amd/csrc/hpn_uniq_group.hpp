@@ -59,10 +59,7 @@ struct UniqDescHost {   // UniqDesc as the host reads it (runs of equal hashes o
 static_assert(sizeof(UniqDescHost) == kUniqDescBytes, "UniqDesc layout");
 }  // namespace hpn
 
-struct hpn_uniq_state {
-    hpn::StoreSession s;
-    int paired = 0;   // s.n_streams - 1
-    uint32_t hash_bits = 0;
+struct hpn_uniq_work {   // what a new session must not inherit: the stage's arrays, the output and what is cached of it
     hpn::Scratch hash, order, djb, sumq, flag, gid, count, best, first, rep, mark, rank, key, val, key_tmp, val_tmp, hist, offs, status,
         list_table, list_key, size, off, out;
     uint32_t N = 0, U = 0;
@@ -70,18 +67,21 @@ struct hpn_uniq_state {
     int cached_which = -1, cached_mate = -1;
 };
 
+struct hpn_uniq_state : hpn::FamilyState, hpn_uniq_work {
+    static constexpr int kSlot = hpn::kStUniq;
+    hpn::StoreSession s;
+    int paired = 0;   // s.n_streams - 1
+    uint32_t hash_bits = 0;
+};
+
 namespace hpn {
 
-inline uint32_t *uniq_kinfo(hpn_uniq_state *u) { return u->s.d_info + kUiBase; }
+inline uint32_t *uniq_kinfo(hpn_uniq_state *u) { return u->s.info.d + kUiBase; }
 
 inline void uniq_drop_session(hpn_uniq_state *u)
 {
     session_drop(u->s);
-    Scratch *ss[] = {&u->hash, &u->order, &u->djb, &u->sumq, &u->flag, &u->gid, &u->count, &u->best, &u->first, &u->rep, &u->mark, &u->rank,
-                     &u->key, &u->val, &u->key_tmp, &u->val_tmp, &u->hist, &u->offs, &u->status, &u->list_table, &u->list_key, &u->size,
-                     &u->off, &u->out};
-    for (Scratch *s : ss) release_scratch(*s);
-    u->cached_which = u->cached_mate = -1;
+    static_cast<hpn_uniq_work &>(*u) = hpn_uniq_work();
 }
 
 // _begin of the three families that group: the session's, and the grouping hash's width
@@ -101,7 +101,7 @@ inline int uniq_sort(hpn_ctx *c, hpn_uniq_state *u, uint64_t *keys, uint32_t *va
         (rc = need(c, u->status, uniq_scan_tiles(hw > n ? hw : n) * 8)) != HPN_OK)
         return rc;
     HPN_HIP(c, uniq_sort_pairs(keys, vals, n, begin_bit, end_bit, (uint64_t *)u->key_tmp.p, (uint32_t *)u->val_tmp.p, (uint32_t *)u->hist.p,
-                               (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.ticket(), u->s.err(), c->stream));
+                               (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(), c->stream));
     return HPN_OK;
 }
 
@@ -156,10 +156,10 @@ inline int uniq_match_mates(hpn_ctx *c, hpn_uniq_state *u, uint32_t *N, int64_t 
     const uint8_t *t0 = u->s.text(0);
     const void *d0 = u->s.m[0].desc.p;
     const uint32_t n2 = (uint32_t)u->s.m[1].n, both = *N < n2 ? *N : n2;
-    HPN_HIP(c, hipMemsetAsync(u->s.d_info + kUiFirstBad, 0xff, sizeof(uint32_t), c->stream));
-    HPN_HIP(c, launch_uniq_names(t0, d0, u->s.text(1), u->s.m[1].desc.p, both, u->s.d_info + kUiFirstBad, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
-    if (u->s.h_info[kUiFirstBad] != 0xffffffffu) *N = u->s.h_info[kUiFirstBad], *unmatched = *N;
+    HPN_HIP(c, hipMemsetAsync(u->s.info.d + kUiFirstBad, 0xff, sizeof(uint32_t), c->stream));
+    HPN_HIP(c, launch_uniq_names(t0, d0, u->s.text(1), u->s.m[1].desc.p, both, u->s.info.d + kUiFirstBad, c->stream));
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
+    if (u->s.info.h[kUiFirstBad] != 0xffffffffu) *N = u->s.info.h[kUiFirstBad], *unmatched = *N;
     else if (*N > n2) *N = n2, *unmatched = n2;   // the mate is missing
     if (*unmatched >= 0) {
         UniqDescHost d;
@@ -190,16 +190,16 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
     uint64_t *hash = (uint64_t *)u->hash.p;
     uint32_t *order = (uint32_t *)u->order.p, *djb = (uint32_t *)u->djb.p, *sumq = (uint32_t *)u->sumq.p, *flag = (uint32_t *)u->flag.p;
     uint32_t *gid = (uint32_t *)u->gid.p, *mark = (uint32_t *)u->mark.p, *rank = (uint32_t *)u->rank.p;
-    uint32_t *ticket = u->s.ticket(), *err = u->s.err();
+    uint32_t *ticket = u->s.info.ticket(), *err = u->s.info.err();
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTally], c->stream));
     const uint64_t mask = u->hash_bits ? (1ull << u->hash_bits) - 1 : ~0ull;
     HPN_HIP(c, launch_uniq_pair(t0, d0, t1, d1, paired, N, mask, hash, order, djb, sumq, uniq_kinfo(u), c->stream));
     if ((rc = uniq_sort(c, u, hash, order, N, 0, u->hash_bits ? (int)u->hash_bits : 64)) != HPN_OK) return rc;
     HPN_HIP(c, launch_uniq_flags(t0, d0, t1, d1, paired, hash, order, N, flag, uniq_kinfo(u), c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
-    *hash_clashes = u->s.h_info[kUiClash];
-    const uint32_t max_len = u->s.h_info[kUiMaxLen];
-    if (u->s.h_info[kUiClash]) {
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
+    *hash_clashes = u->s.info.h[kUiClash];
+    const uint32_t max_len = u->s.info.h[kUiMaxLen];
+    if (u->s.info.h[kUiClash]) {
         if ((rc = uniq_order_clashing_runs(c, u)) != HPN_OK) return rc;
         HPN_HIP(c, launch_uniq_flags(t0, d0, t1, d1, paired, hash, order, N, flag, uniq_kinfo(u), c->stream));
     }
@@ -207,7 +207,7 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
     HPN_HIP(c, uniq_scan32(flag, gid, N, (u64 *)u->status.p, ticket, err, c->stream));
     uint32_t U = 0;
     HPN_HIP(c, hipMemcpyAsync(&U, gid + N, 4, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
     u->U = U;
     if ((rc = need(c, u->count, (size_t)U * 4)) != HPN_OK || (rc = need(c, u->best, (size_t)U * 8)) != HPN_OK ||
         (rc = need(c, u->first, (size_t)U * 4)) != HPN_OK || (rc = need(c, u->rep, (size_t)U * 4)) != HPN_OK ||
@@ -221,7 +221,7 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
                                   uniq_kinfo(u), c->stream));
     HPN_HIP(c, launch_uniq_mark(first, U, mark, N, c->stream));
     HPN_HIP(c, uniq_scan32(mark, rank, N, (u64 *)u->status.p, ticket, err, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
     // the table's size and the parity of its doublings
     auto epoch = [](uint32_t j) { return j < 4 ? 0u : (uint32_t)(31 - __builtin_clz(j)) - 1u; };
     uint64_t S = 0;
@@ -230,7 +230,7 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
         S = 4;
         while (S < U) S *= 2;
         K = epoch(U - 1);
-        if (replace_doubles && U >= 4 && (U & (U - 1)) == 0 && u->s.h_info[kUiBehind]) S *= 2, K += 1;
+        if (replace_doubles && U >= 4 && (U & (U - 1)) == 0 && u->s.info.h[kUiBehind]) S *= 2, K += 1;
     }
     *hash_size = S;
     int slot_bits = 0;
@@ -248,7 +248,7 @@ inline int uniq_group(hpn_ctx *c, hpn_uniq_state *u, bool replace_doubles, uint6
     }
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTally], c->stream));
     c->ev_valid[kFamTally] = true;
-    return info_fetch(c, u->s);
+    return u->s.info.fetch(c);
 }
 
 }  // namespace hpn

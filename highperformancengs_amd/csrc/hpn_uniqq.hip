@@ -24,11 +24,15 @@ hipError_t launch_uniqq_write(const uint8_t *d_text, const void *d_desc, const u
 
 using namespace hpn;
 
-struct hpn_uniqq_state {
-    hpn_uniq_state g;   // single-end: the store, the grouping stage's arrays, the output text
+struct hpn_uniqq_work {   // what a new session must not inherit
     Scratch len, P, start, total, goff, base, list_count;
     bool have_count_list = false;
     uint32_t max_count = 0;
+};
+
+struct hpn_uniqq_state : FamilyState, hpn_uniqq_work {
+    static constexpr int kSlot = kStUniqq;
+    hpn_uniq_state g;   // single-end: the store, the grouping stage's arrays, the output text
 };
 
 namespace {
@@ -36,10 +40,7 @@ namespace {
 void drop_session(hpn_uniqq_state *q)
 {
     uniq_drop_session(&q->g);
-    Scratch *ss[] = {&q->len, &q->P, &q->start, &q->total, &q->goff, &q->base, &q->list_count};
-    for (Scratch *s : ss) release_scratch(*s);
-    q->have_count_list = false;
-    q->max_count = 0;
+    static_cast<hpn_uniqq_work &>(*q) = hpn_uniqq_work();
 }
 
 // -C: count descending, equal counts in the order of the table walk -- one stable sort over the digits of the count that can
@@ -58,7 +59,7 @@ int count_list(hpn_ctx *c, hpn_uniqq_state *q)
     HPN_HIP(c, launch_uniqq_count_key((const uint32_t *)u->list_table.p, (const uint32_t *)u->count.p, U, key, val, c->stream));
     if ((rc = uniq_sort(c, u, key, val, U, 32, 32 + count_bits)) != HPN_OK) return rc;
     HPN_HIP(c, hipMemcpyAsync(q->list_count.p, val, (size_t)U * 4, hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
     q->have_count_list = true;
     return HPN_OK;
 }
@@ -77,11 +78,11 @@ int place_groups(hpn_ctx *c, hpn_uniqq_state *q, int which, uint64_t *total)
     const uint32_t *order = (const uint32_t *)u->order.p, *start = (const uint32_t *)q->start.p, *count = (const uint32_t *)u->count.p;
     const uint64_t *P = (const uint64_t *)q->P.p;
     HPN_HIP(c, launch_uniqq_sizes(u->s.m[0].desc.p, order, list, start, count, P, U, (uint64_t *)q->total.p, c->stream));
-    HPN_HIP(c, uniq_scan64w((const uint64_t *)q->total.p, (uint64_t *)q->goff.p, U, (u64 *)u->status.p, u->s.ticket(), u->s.err(),
+    HPN_HIP(c, uniq_scan64w((const uint64_t *)q->total.p, (uint64_t *)q->goff.p, U, (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(),
                             c->stream));
     HPN_HIP(c, launch_uniqq_base(u->s.m[0].desc.p, order, list, start, count, P, (const uint64_t *)q->goff.p, U, (uint64_t *)q->base.p, c->stream));
     HPN_HIP(c, hipMemcpyAsync(total, (const uint64_t *)q->goff.p + U, 8, hipMemcpyDeviceToHost, c->stream));
-    return info_fetch(c, u->s);
+    return u->s.info.fetch(c);
 }
 
 // the whole text of one output on the device (u->out, u->out_total bytes)
@@ -106,17 +107,6 @@ int build_output(hpn_ctx *c, hpn_uniqq_state *q, int which)
 
 }  // namespace
 
-namespace hpn {
-void uniqq_release(hpn_ctx *c)
-{
-    if (!c->qq) return;
-    drop_session(c->qq);
-    info_free(c->qq->g.s);
-    delete c->qq;
-    c->qq = nullptr;
-}
-}  // namespace hpn
-
 extern "C" {
 
 int hpn_fastq_uniqq_begin(hpn_ctx *c, uint64_t max_bytes, uint32_t hash_bits)
@@ -124,21 +114,22 @@ int hpn_fastq_uniqq_begin(hpn_ctx *c, uint64_t max_bytes, uint32_t hash_bits)
     if (!c) return HPN_E_ARG;
     if (hash_bits > 63) return fail(c, HPN_E_ARG, "hash_bits %u (0 = all 64, or 1 .. 63)", hash_bits);
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->qq) c->qq = new hpn_uniqq_state;
-    drop_session(c->qq);
-    return uniq_begin(c, &c->qq->g, 0, max_bytes, hash_bits);
+    hpn_uniqq_state *q = state_make<hpn_uniqq_state>(c);
+    drop_session(q);
+    return uniq_begin(c, &q->g, 0, max_bytes, hash_bits);
 }
 
 int hpn_fastq_uniqq_add(hpn_ctx *c, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    return session_add(c, c->qq ? &c->qq->g.s : nullptr, "hpn_fastq_uniqq", 0, kUniqDescBytes, launch_uniqq_keys, nullptr, 4u, text, nbytes, last, false, info);
+    hpn_uniqq_state *q = state<hpn_uniqq_state>(c);
+    return session_add(c, q ? &q->g.s : nullptr, "hpn_fastq_uniqq", 0, kUniqDescBytes, frame_by<launch_uniqq_keys>, nullptr, 4u, text, nbytes, last, false, info);
 }
 
 int hpn_fastq_uniqq_finish(hpn_ctx *c, hpn_uniqq_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_uniqq_state *q = c->qq;
+    hpn_uniqq_state *q = state<hpn_uniqq_state>(c);
     hpn_uniq_state *u = q ? &q->g : nullptr;
     int rc;
     if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_uniqq", kUniqDescBytes)) != HPN_OK) return rc;
@@ -153,10 +144,10 @@ int hpn_fastq_uniqq_finish(hpn_ctx *c, hpn_uniqq_result *res)
         (rc = need(c, q->start, (size_t)U * 4)) != HPN_OK || (rc = need(c, u->status, uniq_scan_tiles(N) * 8)) != HPN_OK)
         return rc;
     HPN_HIP(c, launch_uniqq_len(u->s.m[0].desc.p, (const uint32_t *)u->order.p, (const uint32_t *)u->flag.p, (const uint32_t *)u->gid.p,
-                                (const uint32_t *)u->count.p, N, (uint32_t *)q->len.p, (uint32_t *)q->start.p, u->s.d_info + kUiMaxCount, c->stream));
-    HPN_HIP(c, uniq_scan64((const uint32_t *)q->len.p, (uint64_t *)q->P.p, N, (u64 *)u->status.p, u->s.ticket(), u->s.err(), c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
-    res->max_count = q->max_count = u->s.h_info[kUiMaxCount];
+                                (const uint32_t *)u->count.p, N, (uint32_t *)q->len.p, (uint32_t *)q->start.p, u->s.info.d + kUiMaxCount, c->stream));
+    HPN_HIP(c, uniq_scan64((const uint32_t *)q->len.p, (uint64_t *)q->P.p, N, (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(), c->stream));
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
+    res->max_count = q->max_count = u->s.info.h[kUiMaxCount];
     if ((rc = place_groups(c, q, HPN_UNIQQ_KEY_ORDER, &res->out_bytes)) != HPN_OK) return rc;   // (both orders hold the same groups)
     u->s.finished = true;
     return HPN_OK;
@@ -165,7 +156,7 @@ int hpn_fastq_uniqq_finish(hpn_ctx *c, hpn_uniqq_result *res)
 int hpn_fastq_uniqq_write(hpn_ctx *c, int which, uint64_t offset, void *out, uint64_t cap, uint64_t *written)
 {
     if (!c || !written) return HPN_E_ARG;
-    hpn_uniqq_state *q = c->qq;
+    hpn_uniqq_state *q = state<hpn_uniqq_state>(c);
     hpn_uniq_state *u = q ? &q->g : nullptr;
     int rc;
     if ((rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_uniqq", written)) != HPN_OK) return rc;

@@ -28,11 +28,15 @@ hipError_t launch_usort_write(const uint8_t *t0, const void *d0, const uint8_t *
 
 using namespace hpn;
 
-struct hpn_usort_state {
-    hpn_uniq_state g;   // the store, the grouping stage's arrays, the output text
+struct hpn_usort_work {   // what a new session must not inherit
     Scratch djb64, list, size64;
     uint64_t lone_line = 0;   // mate 0 ends with one line without '\n' behind its last record: count_read counts it
     uint32_t seq_len = 0;
+};
+
+struct hpn_usort_state : FamilyState, hpn_usort_work {
+    static constexpr int kSlot = kStUsort;
+    hpn_uniq_state g;   // the store, the grouping stage's arrays, the output text
 };
 
 namespace {
@@ -40,9 +44,7 @@ namespace {
 void drop_session(hpn_usort_state *q)
 {
     uniq_drop_session(&q->g);
-    Scratch *ss[] = {&q->djb64, &q->list, &q->size64};
-    for (Scratch *s : ss) release_scratch(*s);
-    q->lone_line = 0, q->seq_len = 0;
+    static_cast<hpn_usort_work &>(*q) = hpn_usort_work();
 }
 
 // the whole text of one mate's output on the device (u->out, u->out_total bytes)
@@ -59,11 +61,11 @@ int build_output(hpn_ctx *c, hpn_usort_state *q, int mate)
     const void *d0 = u->s.m[0].desc.p, *d1 = paired ? u->s.m[1].desc.p : nullptr;
     const uint32_t *list = (const uint32_t *)q->list.p, *first = (const uint32_t *)u->first.p, *count = (const uint32_t *)u->count.p;
     HPN_HIP(c, launch_usort_sizes(t0, d0, t1, d1, paired, mate, list, first, count, U, q->seq_len, (uint64_t *)q->size64.p, c->stream));
-    HPN_HIP(c, uniq_scan64w((const uint64_t *)q->size64.p, (uint64_t *)u->off.p, U, (u64 *)u->status.p, u->s.ticket(), u->s.err(),
+    HPN_HIP(c, uniq_scan64w((const uint64_t *)q->size64.p, (uint64_t *)u->off.p, U, (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(),
                             c->stream));
     uint64_t total = 0;
     HPN_HIP(c, hipMemcpyAsync(&total, (const uint64_t *)u->off.p + U, 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
     u->cached_mate = -1;
     if ((rc = need(c, u->out, total)) != HPN_OK) return rc;
     HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
@@ -85,17 +87,6 @@ int bits_of(uint64_t v)
 
 }  // namespace
 
-namespace hpn {
-void usort_release(hpn_ctx *c)
-{
-    if (!c->us) return;
-    drop_session(c->us);
-    info_free(c->us->g.s);
-    delete c->us;
-    c->us = nullptr;
-}
-}  // namespace hpn
-
 extern "C" {
 
 int hpn_fastq_usort_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t hash_bits)
@@ -103,17 +94,17 @@ int hpn_fastq_usort_begin(hpn_ctx *c, int paired, uint64_t max_bytes, uint32_t h
     if (!c) return HPN_E_ARG;
     if (hash_bits > 63) return fail(c, HPN_E_ARG, "hash_bits %u (0 = all 64, or 1 .. 63)", hash_bits);
     HPN_HIP(c, hipSetDevice(c->device));
-    if (!c->us) c->us = new hpn_usort_state;
-    drop_session(c->us);
-    return uniq_begin(c, &c->us->g, paired, max_bytes, hash_bits);
+    hpn_usort_state *q = state_make<hpn_usort_state>(c);
+    drop_session(q);
+    return uniq_begin(c, &q->g, paired, max_bytes, hash_bits);
 }
 
 int hpn_fastq_usort_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes, int last, hpn_uniq_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_usort_state *q = c->us;
+    hpn_usort_state *q = state<hpn_usort_state>(c);
     const uint64_t span = q && mate == 0 ? q->g.s.m[0].len - q->g.s.m[0].pos + nbytes : 0;   // (what the call frames, when it gets that far)
-    const int rc = session_add(c, q ? &q->g.s : nullptr, "hpn_fastq_usort", mate, kUniqDescBytes, launch_uniqq_keys, nullptr, 4u, text, nbytes, last, false, info);
+    const int rc = session_add(c, q ? &q->g.s : nullptr, "hpn_fastq_usort", mate, kUniqDescBytes, frame_by<launch_uniqq_keys>, nullptr, 4u, text, nbytes, last, false, info);
     // the line index of the stream's last stretch tells whether one open line follows the last record (k_uniq_keys takes it as
     // no record; count_read's gzgets returns it)
     if (rc == HPN_OK && q->g.s.open && last && mate == 0 && span)
@@ -124,7 +115,7 @@ int hpn_fastq_usort_add(hpn_ctx *c, int mate, const void *text, uint64_t nbytes,
 int hpn_fastq_usort_finish(hpn_ctx *c, hpn_usort_result *res)
 {
     if (!c || !res) return HPN_E_ARG;
-    hpn_usort_state *q = c->us;
+    hpn_usort_state *q = state<hpn_usort_state>(c);
     hpn_uniq_state *u = q ? &q->g : nullptr;
     int rc;
     if ((rc = session_finish_begin(c, u ? &u->s : nullptr, "hpn_fastq_usort", kUniqDescBytes)) != HPN_OK) return rc;
@@ -161,13 +152,13 @@ int hpn_fastq_usort_finish(hpn_ctx *c, hpn_usort_result *res)
     HPN_HIP(c, launch_usort_djb64(t0, d0, t1, d1, paired, first, U, (uint64_t *)q->djb64.p, c->stream));
     HPN_HIP(c, launch_usort_bucket(t0, d0, t1, d1, paired, first, (const uint32_t *)u->rank.p, count, (const uint64_t *)q->djb64.p, U, S, key, val,
                                    uniq_kinfo(u), c->stream));
-    if ((rc = info_fetch(c, u->s)) != HPN_OK) return rc;
-    res->max_count = u->s.h_info[kUiBase + kUsMaxCount];
-    res->seq_len = q->seq_len = u->s.h_info[kUiBase + kUsSeqLen];
-    if (u->s.h_info[kUiBase + kUsLongKey] || u->s.h_info[kUiBase + kUsShortKey]) {
+    if ((rc = u->s.info.fetch(c)) != HPN_OK) return rc;
+    res->max_count = u->s.info.h[kUiBase + kUsMaxCount];
+    res->seq_len = q->seq_len = u->s.info.h[kUiBase + kUsSeqLen];
+    if (u->s.info.h[kUiBase + kUsLongKey] || u->s.info.h[kUiBase + kUsShortKey]) {
         u->s.open = false;
-        res->no_answer = u->s.h_info[kUiBase + kUsLongKey] ? HPN_USORT_LONG_KEY : HPN_USORT_SHORT_KEY;
-        return u->s.h_info[kUiBase + kUsLongKey] ? fail(c, HPN_E_DOMAIN, "a pair's joined sequences have more than 1023 bytes: the reference's key buffer holds 1024")
+        res->no_answer = u->s.info.h[kUiBase + kUsLongKey] ? HPN_USORT_LONG_KEY : HPN_USORT_SHORT_KEY;
+        return u->s.info.h[kUiBase + kUsLongKey] ? fail(c, HPN_E_DOMAIN, "a pair's joined sequences have more than 1023 bytes: the reference's key buffer holds 1024")
                                      : fail(c, HPN_E_DOMAIN, "a pair's joined sequences have fewer than the %u bytes of the first read: the reference prints from behind the key", q->seq_len);
     }
     // the walk: slots ascending, every chain newest first; then count descending over the digits that can differ
@@ -188,7 +179,7 @@ int hpn_fastq_usort_finish(hpn_ctx *c, hpn_usort_result *res)
 int hpn_fastq_usort_write(hpn_ctx *c, int mate, uint64_t offset, void *out, uint64_t cap, uint64_t *written)
 {
     if (!c || !written) return HPN_E_ARG;
-    hpn_usort_state *q = c->us;
+    hpn_usort_state *q = state<hpn_usort_state>(c);
     hpn_uniq_state *u = q ? &q->g : nullptr;
     int rc;
     if ((rc = session_write_begin(c, u ? &u->s : nullptr, "hpn_fastq_usort", written)) != HPN_OK) return rc;

@@ -1,12 +1,16 @@
-"""GPU: what the session layer of csrc/hpn_store.hpp decides for all six store-backed families alike -- hpn_fastq_uniq_*,
-_uniqq_*, _usort_*, _sort_*, _pair_* and hpn_twobit_pack_* -- on three records (ten for usort, which refuses fewer): the byte
-limit, NULL text, chunks cut inside a record, the slice copy's edges, and for sessions of two mates the mate check, the
-unclosed mate and the limit over both.  Expected outputs are the Python restatements', never the library's."""
+"""GPU: what the session layer of csrc/hpn_store.hpp decides for the store-backed families alike -- hpn_fastq_uniq_*, _uniqq_*,
+_usort_*, _sort_*, _pair_*, hpn_twobit_pack_*, hpn_mrle_* and hpn_kseq_* -- on three records (ten for usort, which refuses
+fewer; three of its own for mrle, whose codec knows the six symbols #/7<BF only): the byte limit, NULL text, chunks cut inside a
+record, the slice copy's edges, and for sessions of two mates the mate check, the unclosed mate and the limit over both.
+(hpn_rfastqc_* has its session tests in test_rqc_gpu.py: its fourth call reads typed arrays.)  Expected outputs are the Python
+restatements', never the library's."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import kseq_ref
+import mrle_ref
 import pair_ref
 import sort_ref
 import twobit_ref
@@ -19,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 THREE = b"@a\nACGT\n+\nIIII\n" b"@b\nGGCA\n+\nIIII\n" b"@c\nACGT\n+\nHHHH\n"
 TEN = b"".join(b"@%c\n%s\n+\nIIII\n" % (97 + i, s) for i, s in enumerate([b"ACGT", b"GGCA", b"ACGT", b"TTTT", b"GGCA", b"ACGT", b"CCCC", b"TTTA", b"ACGT", b"GGCA"]))
+MRLE3 = b"@a\nACGT\n+\n##//\n" b"@b\nGGCA\n+\n77<<\n" b"@c\nACGT\n+\nBFFF\n"      # (THREE's I and H are outside the codec's domain)
 FIRST_RECORD = 15      # bytes of THREE's and TEN's first record: the cut below falls inside the second
 
 
@@ -93,6 +98,9 @@ FAMILIES = [
     Family("twobit", "hpn_twobit_pack", _lib.TwobitResult, _lib.SortInfo, 1, THREE, twobit_ref.pack(THREE)[0], lambda mates, max_bytes: (max_bytes,)),
     Family("pair", "hpn_fastq_pair", _lib.PairResult, _lib.SortInfo, 2, THREE, pair_ref.outputs(THREE, THREE, pair_ref.device(THREE, THREE)[1])[0],
            lambda mates, max_bytes: (max_bytes,), True, (0,)),
+    Family("mrle", "hpn_mrle", _lib.MrleResult, _lib.SortInfo, 1, MRLE3, mrle_ref.mrle(MRLE3)[0][mrle_ref.PACKED], lambda mates, max_bytes: (max_bytes,),
+           False, (_lib.MRLE_PACKED,)),
+    Family("kseq", "hpn_kseq", _lib.KseqResult, _lib.SortInfo, 1, THREE, kseq_ref.map_kseq(THREE)[0], lambda mates, max_bytes: (max_bytes,)),
 ]
 PAIRED = [f for f in FAMILIES if f.mates == 2]
 by_name = dict(argvalues=FAMILIES, ids=[f.name for f in FAMILIES])
