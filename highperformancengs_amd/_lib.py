@@ -159,6 +159,16 @@ class SplitResult(C.Structure):
                 ("reason", C.c_uint32), ("n_ref", C.c_uint32)]
 
 
+class BaiInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_runs", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
+                ("reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BaiResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_chunks", C.c_uint64), ("n_windows", C.c_uint64), ("n_no_coor", C.c_uint64), ("bad_record", C.c_int64),
+                ("bad_tid", C.c_int32), ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("n_ref", C.c_uint32)]
+
+
 class GzInfo(C.Structure):
     _fields_ = [("n_bytes", C.c_uint64), ("end_bit", C.c_uint64), ("status", C.c_uint32), ("bad_chunk", C.c_uint32),
                 ("final_chunk", C.c_uint32), ("reserved", C.c_uint32)]
@@ -274,6 +284,10 @@ SYMBOLS = [
     ("hpn_bam_split_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_split_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_split_finish", _int, [_vp, C.POINTER(SplitResult), _vp]),
+    ("hpn_bam_bai_begin", _int, [_vp, _i32, _vp, _u64]),
+    ("hpn_bam_bai_add_raw_dev", _int, [_vp, _vp, _vp, _u64, _vp, _int, _u64, C.POINTER(BaiInfo)]),
+    ("hpn_bam_bai_finish", _int, [_vp, C.POINTER(BaiResult)]),
+    ("hpn_bam_bai_read", _int, [_vp, _vp, _vp, _vp]),
     ("hpn_depth_begin", _int, [_vp, _i32, _u32, _u32]),
     ("hpn_depth_begin_w", _int, [_vp, _i32, _u32, _u32, _u32]),
     ("hpn_depth_progress", _int, [_vp, C.POINTER(_u64)]),
@@ -320,7 +334,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 11:
+    if L.hpn_abi_version() != 12:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

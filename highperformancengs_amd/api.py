@@ -755,6 +755,37 @@ class Context:
         self._ck(self.L.hpn_bam_split_finish(self.h, C.byref(res), _ptr(counts)), "hpn_bam_split_finish")
         return res, counts[:n_ref]
 
+    # ---- samtools index: the .bai of a coordinate-sorted BAM (hpn_bam_bai_*) ----
+    BAI_TARGET = np.dtype([("off_beg", "<u8"), ("off_end", "<u8"), ("n_mapped", "<u8"), ("n_unmapped", "<u8"), ("first_chunk", "<u8"),
+                           ("n_chunks", "<u8"), ("first_window", "<u8"), ("n_windows", "<i4"), ("has_records", "<u4")])
+    BAI_CHUNK = np.dtype([("beg", "<u8"), ("end", "<u8"), ("bin", "<u4"), ("tid", "<i4")])
+
+    def bam_bai_begin(self, target_len, first_voffset):
+        """target_len: the header's target lengths; first_voffset: the virtual offset behind the header."""
+        tl = np.ascontiguousarray(target_len, np.int32)
+        self._ck(self.L.hpn_bam_bai_begin(self.h, len(tl), _ptr(tl) if len(tl) else None, int(first_voffset)), "hpn_bam_bai_begin")
+
+    def bam_bai_add_raw_dev(self, d_raw, d_blocks=None, n_blocks=0, block_addr=(), last=False, end_voffset=0):
+        """The batch hpn_bam_raw_index_dev indexed last with its block table and block_addr[0 .. n_blocks] = the blocks' file offsets
+        and the offset behind the last (d_raw None: no records, only `last` with the file's final virtual offset) -> BaiInfo."""
+        info = _lib.BaiInfo()
+        addr = np.ascontiguousarray(block_addr, np.uint64)
+        assert d_raw is None or len(addr) == n_blocks + 1
+        self._ck(self.L.hpn_bam_bai_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, _ptr(d_blocks) if d_blocks is not None else None,
+                                                int(n_blocks), _ptr(addr) if len(addr) else None, 1 if last else 0, int(end_voffset), C.byref(info)),
+                 "hpn_bam_bai_add_raw_dev")
+        return info
+
+    def bam_bai_finish(self):
+        """-> (BaiResult, targets, chunks, windows): structured arrays of BAI_TARGET / BAI_CHUNK and the linear index's offsets."""
+        res = _lib.BaiResult()
+        self._ck(self.L.hpn_bam_bai_finish(self.h, C.byref(res)), "hpn_bam_bai_finish")
+        targets, chunks = np.zeros(res.n_ref, self.BAI_TARGET), np.zeros(res.n_chunks, self.BAI_CHUNK)
+        windows = np.zeros(res.n_windows, np.uint64)
+        self._ck(self.L.hpn_bam_bai_read(self.h, _ptr(targets) if res.n_ref else None, _ptr(chunks) if res.n_chunks else None,
+                                         _ptr(windows) if res.n_windows else None), "hpn_bam_bai_read")
+        return res, targets, chunks, windows
+
     # ---- collectives / synthetic -----------------------------------------
     def comm_init(self, rank, n_ranks, unique_id: bytes):
         buf = (C.c_uint8 * _lib.UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

@@ -77,6 +77,15 @@ public:
     void allow_carry(bool on) { carry_ok_ = on, carry_n_ = 0; }
     void drop_carry() { carry_n_ = 0; }                  // (behind a seek: the next launch starts at a record of its own)
     size_t carried() const { return carry_n_; }          // != 0 at the end of the file: it ends inside a record
+    // The last launch's block table as the record index saw it (out_off moved up by the carried bytes), for a caller that asks
+    // where in the FILE a stream position lies (bam_index): block_rel()[i] = block i's offset in the file relative to block 0's,
+    // block_rel()[n_blocks()] = the offset behind the last block; empty_blocks() = blocks of no bytes among them.
+    const hpn_bgzf_block *d_blocks() const { return (const hpn_bgzf_block *)d_blocks_; }
+    size_t n_blocks() const { return last_nb_; }
+    const std::vector<uint64_t> &block_rel() const { return block_rel_; }
+    size_t empty_blocks() const { return n_empty_; }
+    bool last_block_empty() const { return last_empty_; }
+    void no_launch() { last_nb_ = 0, n_empty_ = 0, last_empty_ = false, block_rel_.assign(1, 0); }   // next() gave a batch without blocks
     static constexpr size_t kMaxCarry = (size_t)4 << 20; // the longest unfinished record kept from launch to launch
 
     // Bytes and table to the device, inflate, then (records) index or (text) check every block.
@@ -141,6 +150,12 @@ private:
                bool text_mode, bool may_carry, hpn_raw_info *info)
     {
         memset(info, 0, sizeof *info);
+        last_nb_ = nb, n_empty_ = 0, last_empty_ = false;
+        block_rel_.assign(nb + 1, 0);
+        for (size_t i = 0; i < nb; ++i) {        // (the blocks lie one behind the other in the file: 12 + XLEN bytes, the payload, CRC-32 and ISIZE)
+            block_rel_[i + 1] = table[i].in_off + table[i].in_len + 8 - (table[0].in_off - 18);
+            n_empty_ += table[i].out_len == 0, last_empty_ = table[i].out_len == 0;
+        }
         if (!nb) return 1;
         const size_t h = may_carry && !text_mode ? carry_n_ : 0;      // bytes of the record the launch before ended in
         if (!reserve<hpn_bgzf_block>(d_blocks_, cap_blocks_, nb) ||
@@ -214,8 +229,9 @@ private:
     size_t pad_front_ = 0, pad_back_ = 0;
     std::vector<uint32_t> status_;
     void *d_comp_ = nullptr, *d_blocks_ = nullptr, *d_out_ = nullptr, *d_status_ = nullptr, *h_blocks_ = nullptr, *d_carry_ = nullptr;
-    size_t carry_n_ = 0;
-    bool carry_ok_ = false;
+    size_t carry_n_ = 0, last_nb_ = 0, n_empty_ = 0;
+    bool carry_ok_ = false, last_empty_ = false;
+    std::vector<uint64_t> block_rel_;
     size_t cap_comp_ = 0, cap_blocks_ = 0, cap_out_ = 0, cap_status_ = 0, h_blocks_cap_ = 0;
 };
 
@@ -248,6 +264,7 @@ public:
             if (fread(h, 1, 18, f) != 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') break;
             const uint32_t bsize = (h[16] | (h[17] << 8)) + 1u, xlen = h[10] | (h[11] << 8);
             if (bsize < xlen + 20u || xlen < 6u) break;
+            if (!plain_header(h)) odd_headers_ = true;
             raw.resize(bsize - 18);
             if (fread(raw.data(), 1, raw.size(), f) != raw.size()) break;
             uint32_t isize;
@@ -278,7 +295,7 @@ public:
         chunk_ = default_chunk(chunk);
         pump_.reset(new TextPump(ctx, path, chunk_, nbuf, true));
         if (!pump_->ok()) return false;
-        skip_ = start_;
+        skip_ = start_, first_off0_ = first_off_, batch_at_ = file_next_ = start_;
         dev_.allow_carry(true);                 // one stream, batches in file order: records may run from one launch into the next
         {   // launches of 44 chunks only where the file is long enough to pay for them: a launch twice as long also ends the file
             // with twice the work behind the last upload and starts it with a longer ramp (+ 20 - 50 ms of wall on a 10.6 GB
@@ -324,6 +341,13 @@ public:
     }
 
     const uint8_t *d_raw() const { return dev_.d_raw(); }
+    // For bam_index (a stream read front to back, never after seek()): the virtual offset of the first record, the device side
+    // of the batch next() returned last, the file offset of its first block, and whether every block header seen so far is the
+    // 18-byte one samtools' reader insists on (XLEN 6, one BC field of 2 bytes).
+    uint64_t first_voffset() const { return start_ << 16 | first_off0_; }
+    const BgzfDevice &device() const { return dev_; }
+    uint64_t batch_file_offset() const { return batch_at_; }
+    bool plain_headers() const { return !odd_headers_; }
     // chunks under one inflate launch, for a caller that knows better than the default (HPN_BAM_ROUNDS overrides both)
     void prefer_rounds(int n) { if (!rounds_env() && n > 0 && !producer_.joinable()) rounds_ = n; }   // (before start())
 
@@ -341,8 +365,13 @@ public:
             BgzfStage none;
             const int r = gather(nullptr, none);
             if (r != 1) return r;
-            if (!dev_.blocks_added()) return eof_ ? (dev_.carried() ? -1 : 0) : 1;   // (a batch may be empty; a file may not end inside a record)
-            return dev_.finish(text_mode_, info);
+            if (!dev_.blocks_added()) {
+                dev_.no_launch();
+                return eof_ ? (dev_.carried() ? -1 : 0) : 1;   // (a batch may be empty; a file may not end inside a record)
+            }
+            const int rf = dev_.finish(text_mode_, info);
+            batch_at_ = file_next_, file_next_ += dev_.block_rel().back();
+            return rf;
         }
         if (ended_) return final_;                       // (the end, or a failure, has been handed out: it stays)
         if (!producer_.joinable() && !start_producer()) return -1;
@@ -354,7 +383,12 @@ public:
         }
         int r = st.result;
         last_eof_ = st.eof;
-        if (r == 1 && !st.pieces.empty()) r = dev_.finish_stage(st, text_mode_, info);
+        if (r == 1 && !st.pieces.empty()) {
+            r = dev_.finish_stage(st, text_mode_, info);
+            batch_at_ = file_next_, file_next_ += dev_.block_rel().back();
+        } else {
+            dev_.no_launch();
+        }
         stamp("BGZF: launch inflated and indexed");
         if (r == 0 && dev_.carried()) r = -1;            // the file ends inside a record: the host route reports it as the reference does
         {   // the launch has read the stage's bytes (finish_stage waits for its kernels): the producer may fill it again
@@ -562,6 +596,7 @@ private:
             carry_.insert(carry_.end(), p + done, p + done + more);
             done += more;
             if (!add_block(pb, carry_.data(), 0, bsize)) return -1;
+            if (!plain_header(carry_.data())) odd_headers_ = true;
             pb.carry.assign(carry_.begin(), carry_.begin() + bsize);
             in = bsize;
             carry_.clear();
@@ -572,6 +607,7 @@ private:
             const uint32_t bsize = (p[q + 16] | (p[q + 17] << 8)) + 1u;
             if (q + bsize > n) break;
             if (!add_block(pb, p + q, in + (q - done), bsize)) return -1;
+            if (!plain_header(p + q)) odd_headers_ = true;
             q += bsize;
         }
         pb.body_len = q - done;
@@ -581,6 +617,7 @@ private:
         return 1;
     }
 
+    static bool plain_header(const uint8_t *h) { return (h[10] | h[11] << 8) == 6 && (h[14] | h[15] << 8) == 2; }
     static bool add_block(BgzfParsed &pb, const uint8_t *h, uint64_t in_off, uint32_t bsize)
     {
         if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') return false;
@@ -605,6 +642,9 @@ private:
     size_t chunk_ = 0;
     uint64_t start_ = 0, skip_ = 0;  // file offset of the block holding the first record
     uint32_t first_off_ = 0;         // ... and the record's offset inside it
+    uint32_t first_off0_ = 0;        // (as open() found it: first_off_ is used up by the first batch)
+    uint64_t batch_at_ = 0, file_next_ = 0;   // file offset of the last batch's first block, and of the block behind its last
+    bool odd_headers_ = false;
     bool eof_ = false, text_mode_ = false;
     // Pinned chunks of 32 MiB (round 4: 88 MiB -- three of them cost 50 ms to pin in front of the file's first byte and as much
     // again when the process ends), 22 of them = ~700 MiB of compressed bytes under one inflate launch when the file is read

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 11
+#define HPN_ABI_VERSION 12
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -1003,6 +1003,61 @@ int hpn_bam_split_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uin
 int hpn_bam_split_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
 int hpn_bam_split_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
 int hpn_bam_split_finish(hpn_ctx *ctx, hpn_split_result *res, uint64_t *counts /* [n_ref] records per target, may be NULL */);
+
+/* ---- samtools index: the .bai of a coordinate-sorted BAM ---------------------------------------
+ * bam_index.c (samtools-0.1.19): bam_index_core's pass over the records on the device -- every record's virtual offset, the
+ * runs of equal (refID, stored bin) that become chunks, the linear index, the per-target counts of the metadata bin 37450 --
+ * and merge_chunks / fill_missing behind it.  (docs/kernels/bam_bai.md)
+ *   hpn_bam_bai_begin(n_ref, target_len, first_voffset)      first_voffset: bam_tell behind the header
+ *   per batch: hpn_bam_raw_index_dev(...), then hpn_bam_bai_add_raw_dev(d_raw, d_blocks, n_blocks, block_addr, last,
+ *              end_voffset, &info) with the SAME block table (out_off as the record index saw it: moved up by the bytes of a
+ *              carried record) and block_addr[0 .. n_blocks] (host) = the blocks' offsets in the file and the offset behind
+ *              the last one.  A record's start is the end of the record before it, across calls; the end of a record whose
+ *              last byte lies in block k is block_addr[k] << 16 | bytes into the block, and block_addr[k + 1] << 16 where it
+ *              ends with the block.  d_raw NULL: no records.  last != 0 ends the file: end_voffset is what bam_tell says
+ *              behind the failed read at the end of the file (file size << 16 for a file that ends with its data or with
+ *              one empty block).
+ *   hpn_bam_bai_finish(&res), hpn_bam_bai_read(targets, chunks, windows)
+ * Results: per target (hpn_bai_target) the metadata -- off_beg / off_end, n_mapped / n_unmapped (flag & 4), has_records --,
+ * its merged chunks chunks[first_chunk, + n_chunks) sorted by bin and, inside a bin, in file order, and its linear index
+ * windows[first_window, + n_windows) with empty windows filled from the left (n_windows is set by the target's LAST mapped
+ * record, not the largest).  The metadata bin is not among the chunks.
+ * Domain: refID in [-1, n_ref) and never decreasing, -1 behind every placed record; pos >= 0 and never decreasing inside a
+ * target; every mapped record's last window within (target_len - 1) >> 14; no CIGAR operation `B`; no stored bin 37450.  (A block of
+ * no bytes ends the stream for samtools' reader: the caller hands none over except as the file's last.)  The first offending record since _begin is reported -- bad_record (ordinal, -1: none), bad_tid,
+ * bad_pos, reason (1 refID out of range, 2 pos negative, 3 refID goes backwards, 4 pos goes backwards, 5 window beyond the
+ * target, 6 CIGAR `B`, 7 stored bin 37450, 8 name and CIGAR do not fit the record, 9 more than 2^27 runs: bad_record is then the
+ * first record of the batch that went over) -- and the session makes nothing more: the caller indexes the file on the host
+ * (csrc/host/bai_build.hpp), which follows the reference everywhere.  Synchronous. */
+typedef struct hpn_bai_info {
+    uint64_t n_records;      /* records of this batch */
+    uint64_t n_runs;         /* runs of equal (refID, bin) that start in this batch */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, reserved;
+} hpn_bai_info;
+typedef struct hpn_bai_chunk {
+    uint64_t beg, end;       /* virtual offsets */
+    uint32_t bin;
+    int32_t tid;
+} hpn_bai_chunk;
+typedef struct hpn_bai_target {
+    uint64_t off_beg, off_end, n_mapped, n_unmapped;
+    uint64_t first_chunk, n_chunks, first_window;
+    int32_t n_windows;
+    uint32_t has_records;
+} hpn_bai_target;
+typedef struct hpn_bai_result {
+    uint64_t n_records, n_chunks, n_windows, n_no_coor; /* since _begin; n_chunks, n_windows: entries hpn_bam_bai_read fills */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, n_ref;
+} hpn_bai_result;
+int hpn_bam_bai_begin(hpn_ctx *ctx, int32_t n_ref, const int32_t *target_len, uint64_t first_voffset);
+int hpn_bam_bai_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw, const hpn_bgzf_block *d_blocks, uint64_t n_blocks, const uint64_t *block_addr,
+                            int last, uint64_t end_voffset, hpn_bai_info *info);
+int hpn_bam_bai_finish(hpn_ctx *ctx, hpn_bai_result *res);
+int hpn_bam_bai_read(hpn_ctx *ctx, hpn_bai_target *targets /* [n_ref] */, hpn_bai_chunk *chunks /* [n_chunks] */, uint64_t *windows /* [n_windows] */);
 
 /* ---- multi-GPU reduction of count vectors -----------------------------------
  * One RCCL communicator per context; `unique_id` is the 128-byte ncclUniqueId
