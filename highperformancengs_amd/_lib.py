@@ -229,6 +229,9 @@ SYMBOLS = [
     ("hpn_fastq_uniq_finish", _int, [_vp, C.POINTER(UniqResult)]),
     ("hpn_fastq_uniq_write", _int, [_vp, _int, _int, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_sort_pairs_u64", _int, [_vp, _vp, _vp, _u64]),
+    ("hpn_sort_pairs_u64_bits", _int, [_vp, _vp, _vp, _u64, _int, _int]),
+    ("hpn_sort_pairs_u64_digits", _int, [_vp, _vp, _vp, _u64, _u32]),
+    ("hpn_excl_scan", _int, [_vp, _vp, _int, _vp, _int, _u64]),
     ("hpn_fastq_uniqq_begin", _int, [_vp, _u64, _u32]),
     ("hpn_fastq_uniqq_add", _int, [_vp, _vp, _u64, _int, C.POINTER(UniqInfo)]),
     ("hpn_fastq_uniqq_finish", _int, [_vp, C.POINTER(UniqqResult)]),
@@ -334,7 +337,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 12:
+    if L.hpn_abi_version() != 13:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

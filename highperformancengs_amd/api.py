@@ -553,6 +553,33 @@ class Context:
         self._ck(self.L.hpn_sort_pairs_u64(self.h, _ptr(keys) if keys.size else None, _ptr(vals) if keys.size else None, keys.size), "hpn_sort_pairs_u64")
         return keys, vals
 
+    def sort_pairs_bits(self, keys, vals, begin_bit, end_bit):
+        """sort_pairs by the key bits [begin_bit, end_bit) only (hpn_sort_pairs_u64_bits); returns copies."""
+        keys, vals = np.array(keys, np.uint64), np.array(vals, np.uint32)
+        assert keys.shape == vals.shape and keys.ndim == 1
+        self._ck(self.L.hpn_sort_pairs_u64_bits(self.h, _ptr(keys) if keys.size else None, _ptr(vals) if keys.size else None, keys.size,
+                                                int(begin_bit), int(end_bit)), "hpn_sort_pairs_u64_bits")
+        return keys, vals
+
+    def sort_pairs_digits(self, keys, vals, digits):
+        """sort_pairs by the key bytes whose bit is set in digits (hpn_sort_pairs_u64_digits); returns copies."""
+        keys, vals = np.array(keys, np.uint64), np.array(vals, np.uint32)
+        assert keys.shape == vals.shape and keys.ndim == 1
+        self._ck(self.L.hpn_sort_pairs_u64_digits(self.h, _ptr(keys) if keys.size else None, _ptr(vals) if keys.size else None, keys.size,
+                                                  int(digits)), "hpn_sort_pairs_u64_digits")
+        return keys, vals
+
+    def excl_scan(self, values, out_bits=None):
+        """The n + 1 exclusive prefix sums of a uint32 or uint64 array on the device (hpn_excl_scan), as uint32 (modulo 2^32)
+        or uint64; out_bits defaults to the input's width."""
+        values = np.ascontiguousarray(values)
+        assert values.ndim == 1 and values.dtype in (np.uint32, np.uint64)
+        in_bits = values.dtype.itemsize * 8
+        out_bits = in_bits if out_bits is None else int(out_bits)
+        out = np.empty(values.size + 1, np.uint32 if out_bits == 32 else np.uint64)
+        self._ck(self.L.hpn_excl_scan(self.h, _ptr(values) if values.size else None, in_bits, _ptr(out), out_bits, values.size), "hpn_excl_scan")
+        return out
+
     # ---- one stream framed by several contexts: pieces ---------------------------------
     def text_piece_lines(self, text, head, own_bytes, last=False):
         """First half of a piece (hpn_fastq_text_piece_lines): text = head byte + piece + tail; returns hpn_text_piece."""

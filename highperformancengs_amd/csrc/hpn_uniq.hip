@@ -1,5 +1,5 @@
 // hpn_uniq.hip -- C ABI of duplicate removal (gzfastq_uniq.c): hpn_fastq_uniq_begin / _add / _finish / _write, and
-// hpn_sort_pairs_u64 (the radix sort on its own).  Kernels: kernels/fastq_uniq.hip, kernels/radix_sort.hpp,
+// hpn_sort_pairs_u64 / _bits / _digits and hpn_excl_scan (the radix sort and the prefix scan on their own).  Kernels: kernels/fastq_uniq.hip, kernels/radix_sort.hpp,
 // the line index of kernels/fastq_text.hip.
 //
 // The stream's bytes are appended to a device store as they come (the reference keeps every record in memory too), so a
@@ -31,6 +31,41 @@ int build_output(hpn_ctx *c, hpn_uniq_state *u, int which, int mate)
     u->out_total = total;
     u->cached_which = which, u->cached_mate = mate;
     return HPN_OK;
+}
+
+// The state the primitives' own entry points run in: the uniq family's work space, which a collecting session has in use.
+int prim_state(hpn_ctx *c, hpn_uniq_state **out)
+{
+    hpn_uniq_state *u = state_make<hpn_uniq_state>(c);
+    const int rc = u->s.info.alloc(c);
+    if (rc != HPN_OK) return rc;
+    if (u->s.open && !u->s.finished) return fail(c, HPN_E_STATE, "a hpn_fastq_uniq session is collecting text: its work space is in use");
+    *out = u;
+    return HPN_OK;
+}
+
+// hpn_sort_pairs_u64_*: the caller's n pairs onto the device, sort(u, keys, vals) over them there, and back
+template <typename Sort>
+int sort_pairs_call(hpn_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t n, Sort sort)
+{
+    if (n && (!keys || !vals)) return HPN_E_ARG;
+    if (n >= (1ull << 31)) return fail(c, HPN_E_DOMAIN, "2^31 or more keys");
+    HPN_HIP(c, hipSetDevice(c->device));
+    hpn_uniq_state *u = nullptr;
+    int rc = prim_state(c, &u);
+    if (rc != HPN_OK) return rc;
+    Scratch k, v;   // the caller's arrays on the device, for this call only
+    if ((rc = need(c, k, (size_t)n * 8)) != HPN_OK || (rc = need(c, v, (size_t)n * 4)) != HPN_OK || (rc = u->s.info.zero(c)) != HPN_OK) return rc;
+    if (n) {
+        HPN_HIP(c, hipMemcpyAsync(k.p, keys, (size_t)n * 8, hipMemcpyDefault, c->stream));
+        HPN_HIP(c, hipMemcpyAsync(v.p, vals, (size_t)n * 4, hipMemcpyDefault, c->stream));
+    }
+    if ((rc = sort(u, (uint64_t *)k.p, (uint32_t *)v.p)) != HPN_OK) return rc;
+    if (n) {
+        HPN_HIP(c, hipMemcpyAsync(keys, k.p, (size_t)n * 8, hipMemcpyDefault, c->stream));
+        HPN_HIP(c, hipMemcpyAsync(vals, v.p, (size_t)n * 4, hipMemcpyDefault, c->stream));
+    }
+    return u->s.info.fetch(c);   // (waits for the stream: the arrays are free to go)
 }
 
 }  // namespace
@@ -91,26 +126,50 @@ int hpn_fastq_uniq_write(hpn_ctx *c, int which, int mate, uint64_t offset, void 
     return session_write_slice(c, u->out, u->out_total, offset, out, cap, written);
 }
 
-int hpn_sort_pairs_u64(hpn_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t n)
+int hpn_sort_pairs_u64(hpn_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t n) { return hpn_sort_pairs_u64_bits(c, keys, vals, n, 0, 64); }
+
+int hpn_sort_pairs_u64_bits(hpn_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t n, int begin_bit, int end_bit)
 {
-    if (!c || (n && (!keys || !vals))) return HPN_E_ARG;
-    if (n >= (1ull << 31)) return fail(c, HPN_E_DOMAIN, "2^31 or more keys");
+    if (!c) return HPN_E_ARG;
+    if (begin_bit < 0 || begin_bit > end_bit || end_bit > 64) return fail(c, HPN_E_ARG, "key bits [%d, %d): 0 <= begin <= end <= 64", begin_bit, end_bit);
+    return sort_pairs_call(c, keys, vals, n, [&](hpn_uniq_state *u, uint64_t *k, uint32_t *v) { return uniq_sort(c, u, k, v, (uint32_t)n, begin_bit, end_bit); });
+}
+
+int hpn_sort_pairs_u64_digits(hpn_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t n, uint32_t digits)
+{
+    if (!c) return HPN_E_ARG;
+    if (digits > 255u) return fail(c, HPN_E_ARG, "digit mask %u: a key has 8 bytes", digits);
+    return sort_pairs_call(c, keys, vals, n, [&](hpn_uniq_state *u, uint64_t *k, uint32_t *v) {
+        int rc;
+        if ((rc = uniq_sort_space(c, u, (uint32_t)n)) != HPN_OK) return rc;
+        HPN_HIP(c, uniq_sort_pairs_digits(k, v, (uint32_t)n, digits, (uint64_t *)u->key_tmp.p, (uint32_t *)u->val_tmp.p, (uint32_t *)u->hist.p,
+                                          (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(), c->stream));
+        return (int)HPN_OK;
+    });
+}
+
+int hpn_excl_scan(hpn_ctx *c, const void *in, int in_bits, void *out, int out_bits, uint64_t n)
+{
+    if (!c || !out || (n && !in)) return HPN_E_ARG;
+    if (!((in_bits == 32 && (out_bits == 32 || out_bits == 64)) || (in_bits == 64 && out_bits == 64)))
+        return fail(c, HPN_E_ARG, "scan of %d-bit items into %d-bit sums: 32 -> 32, 32 -> 64 or 64 -> 64", in_bits, out_bits);
+    if (n >= (1ull << 31)) return fail(c, HPN_E_DOMAIN, "2^31 or more items");
     HPN_HIP(c, hipSetDevice(c->device));
-    hpn_uniq_state *u = state_make<hpn_uniq_state>(c);
-    int rc = u->s.info.alloc(c);
+    hpn_uniq_state *u = nullptr;
+    int rc = prim_state(c, &u);
     if (rc != HPN_OK) return rc;
-    if (u->s.open && !u->s.finished) return fail(c, HPN_E_STATE, "a hpn_fastq_uniq session is collecting text: its work space is in use");
-    Scratch k, v;   // the caller's arrays on the device, for this call only
-    if ((rc = need(c, k, (size_t)n * 8)) != HPN_OK || (rc = need(c, v, (size_t)n * 4)) != HPN_OK || (rc = u->s.info.zero(c)) != HPN_OK) return rc;
-    if (n) {
-        HPN_HIP(c, hipMemcpyAsync(k.p, keys, (size_t)n * 8, hipMemcpyDefault, c->stream));
-        HPN_HIP(c, hipMemcpyAsync(v.p, vals, (size_t)n * 4, hipMemcpyDefault, c->stream));
-    }
-    if ((rc = uniq_sort(c, u, (uint64_t *)k.p, (uint32_t *)v.p, (uint32_t)n, 0, 64)) != HPN_OK) return rc;
-    if (n) {
-        HPN_HIP(c, hipMemcpyAsync(keys, k.p, (size_t)n * 8, hipMemcpyDefault, c->stream));
-        HPN_HIP(c, hipMemcpyAsync(vals, v.p, (size_t)n * 4, hipMemcpyDefault, c->stream));
-    }
+    const size_t ib = (size_t)in_bits / 8, ob = (size_t)out_bits / 8;
+    Scratch a, b;   // the caller's arrays on the device, for this call only
+    if ((rc = need(c, a, (size_t)n * ib)) != HPN_OK || (rc = need(c, b, ((size_t)n + 1) * ob)) != HPN_OK ||
+        (rc = need(c, u->status, uniq_scan_tiles(n) * 8)) != HPN_OK || (rc = u->s.info.zero(c)) != HPN_OK)
+        return rc;
+    if (n) HPN_HIP(c, hipMemcpyAsync(a.p, in, (size_t)n * ib, hipMemcpyDefault, c->stream));
+    u64 *status = (u64 *)u->status.p;
+    uint32_t *ticket = u->s.info.ticket(), *err = u->s.info.err();
+    if (in_bits == 64) HPN_HIP(c, uniq_scan64w((const uint64_t *)a.p, (uint64_t *)b.p, n, status, ticket, err, c->stream));
+    else if (out_bits == 64) HPN_HIP(c, uniq_scan64((const uint32_t *)a.p, (uint64_t *)b.p, n, status, ticket, err, c->stream));
+    else HPN_HIP(c, uniq_scan32((const uint32_t *)a.p, (uint32_t *)b.p, n, status, ticket, err, c->stream));
+    HPN_HIP(c, hipMemcpyAsync(out, b.p, ((size_t)n + 1) * ob, hipMemcpyDefault, c->stream));
     return u->s.info.fetch(c);   // (waits for the stream: the arrays are free to go)
 }
 

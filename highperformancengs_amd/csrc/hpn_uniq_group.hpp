@@ -92,7 +92,8 @@ inline int uniq_begin(hpn_ctx *c, hpn_uniq_state *u, int paired, uint64_t max_by
     return rc;
 }
 
-inline int uniq_sort(hpn_ctx *c, hpn_uniq_state *u, uint64_t *keys, uint32_t *vals, uint32_t n, int begin_bit, int end_bit)
+// the work space of one sort of n pairs (kernels/radix_sort.hpp: SortSpace)
+inline int uniq_sort_space(hpn_ctx *c, hpn_uniq_state *u, uint32_t n)
 {
     int rc;
     const uint64_t hw = uniq_sort_hist_words(n);
@@ -100,6 +101,13 @@ inline int uniq_sort(hpn_ctx *c, hpn_uniq_state *u, uint64_t *keys, uint32_t *va
         (rc = need(c, u->hist, hw * 4)) != HPN_OK || (rc = need(c, u->offs, hw * 4)) != HPN_OK ||
         (rc = need(c, u->status, uniq_scan_tiles(hw > n ? hw : n) * 8)) != HPN_OK)
         return rc;
+    return HPN_OK;
+}
+
+inline int uniq_sort(hpn_ctx *c, hpn_uniq_state *u, uint64_t *keys, uint32_t *vals, uint32_t n, int begin_bit, int end_bit)
+{
+    int rc;
+    if ((rc = uniq_sort_space(c, u, n)) != HPN_OK) return rc;
     HPN_HIP(c, uniq_sort_pairs(keys, vals, n, begin_bit, end_bit, (uint64_t *)u->key_tmp.p, (uint32_t *)u->val_tmp.p, (uint32_t *)u->hist.p,
                                (uint32_t *)u->offs.p, (u64 *)u->status.p, u->s.info.ticket(), u->s.info.err(), c->stream));
     return HPN_OK;

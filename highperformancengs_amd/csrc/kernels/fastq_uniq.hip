@@ -525,10 +525,10 @@ hipError_t uniq_sort_pairs_digits(uint64_t *d_keys, uint32_t *d_vals, uint32_t n
     uint32_t *va = d_vals, *vb = d_vals_tmp;
     for (int d = 0; d < 8; ++d) {
         if (!((digits >> d) & 1u)) continue;
-        hipLaunchKernelGGL(k_radix_hist, dim3(grid), dim3(kSortThreads), 0, s, ka, n, 8 * d, tiles, d_hist);
+        hipLaunchKernelGGL(k_radix_hist, dim3(grid), dim3(kSortThreads), 0, s, ka, n, 8 * d, 255u, tiles, d_hist);
         hipError_t e = launch_excl_scan<uint32_t, uint32_t>(d_hist, d_offs, hw, d_status, d_ticket, d_err, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_radix_scatter, dim3(grid), dim3(kSortThreads), 0, s, ka, va, n, 8 * d, tiles, d_offs, kb, vb);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(grid), dim3(kSortThreads), 0, s, ka, va, n, 8 * d, 255u, tiles, d_offs, kb, vb);
         std::swap(ka, kb);
         std::swap(va, vb);
     }

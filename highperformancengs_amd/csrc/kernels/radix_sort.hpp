@@ -86,7 +86,7 @@ hipError_t launch_excl_scan(const TIn *d_in, TOut *d_out, uint64_t n, u64 *d_sta
 }
 
 __global__ __launch_bounds__(kSortThreads) void k_radix_hist(const uint64_t *__restrict__ keys, uint32_t n, int shift,
-                                                             uint32_t tiles, uint32_t *__restrict__ hist)
+                                                             uint32_t mask, uint32_t tiles, uint32_t *__restrict__ hist)
 {
     __shared__ uint32_t s_h[kSortThreads / kWave][256];
     const int w = wave_id(), lane = lane_id();
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kSortThreads) void k_radix_hist(const uint64_t *__r
         const uint32_t i0 = tile * kSortTile;
         for (uint32_t r = 0; r < kSortRounds; ++r) {
             const uint32_t i = i0 + r * kWave + (uint32_t)lane;
-            if (i < n) atomicAdd(&s_h[w][(keys[i] >> shift) & 255u], 1u);
+            if (i < n) atomicAdd(&s_h[w][(uint32_t)(keys[i] >> shift) & mask], 1u);
         }
     }
     __syncthreads();
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(kSortThreads) void k_radix_hist(const uint64_t *__r
 }
 
 __global__ __launch_bounds__(kSortThreads) void k_radix_scatter(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
-                                                                uint32_t n, int shift, uint32_t tiles,
+                                                                uint32_t n, int shift, uint32_t mask, uint32_t tiles,
                                                                 const uint32_t *__restrict__ offs, uint64_t *__restrict__ keys_out,
                                                                 uint32_t *__restrict__ vals_out)
 {
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kSortThreads) void k_radix_scatter(const uint64_t *
         const bool have = live && i < n;
         uint64_t k = 0;
         uint32_t v = 0, d = 0;
-        if (have) k = keys[i], v = vals[i], d = (uint32_t)(k >> shift) & 255u;
+        if (have) k = keys[i], v = vals[i], d = (uint32_t)(k >> shift) & mask;
         u64 same = __ballot(have);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -157,7 +157,8 @@ struct SortSpace {
     uint32_t *ticket, *err;  // one word each (err: see k_excl_scan)
 };
 
-// Sorts (keys, vals) by the key bits [begin_bit, end_bit) in place (stable).
+// Sorts (keys, vals) by the key bits [begin_bit, end_bit) in place (stable) and by no others: the last pass's digit is as wide
+// as what is left of the range.
 inline hipError_t radix_sort_pairs(uint64_t *d_keys, uint32_t *d_vals, uint32_t n, int begin_bit, int end_bit, const SortSpace &ws,
                                    hipStream_t s)
 {
@@ -169,10 +170,11 @@ inline hipError_t radix_sort_pairs(uint64_t *d_keys, uint32_t *d_vals, uint32_t 
     uint32_t *va = d_vals, *vb = ws.vals_tmp;
     int pass = 0;
     for (int shift = begin_bit; shift < end_bit; shift += 8, ++pass) {
-        hipLaunchKernelGGL(k_radix_hist, dim3(grid), dim3(kSortThreads), 0, s, ka, n, shift, tiles, ws.hist);
+        const uint32_t mask = (1u << (end_bit - shift < 8 ? end_bit - shift : 8)) - 1u;
+        hipLaunchKernelGGL(k_radix_hist, dim3(grid), dim3(kSortThreads), 0, s, ka, n, shift, mask, tiles, ws.hist);
         hipError_t e = launch_excl_scan<uint32_t, uint32_t>(ws.hist, ws.offs, hw, ws.status, ws.ticket, ws.err, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_radix_scatter, dim3(grid), dim3(kSortThreads), 0, s, ka, va, n, shift, tiles, ws.offs, kb, vb);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(grid), dim3(kSortThreads), 0, s, ka, va, n, shift, mask, tiles, ws.offs, kb, vb);
         std::swap(ka, kb);
         std::swap(va, vb);
     }

@@ -7,6 +7,12 @@
 // acquire fence needed: MI355X_MICROARCH.md "R2 granule").  The per-XCD L2s are
 // not coherent, hence the agent-scope (sc1) accesses.  Spins are bounded: a
 // hand-off that never arrives sets *err instead of hanging the GPU.
+//
+// Precondition: the granule carries 62 bits of value, so the total of a scan
+// must stay below 2^62 (2^62 - 1 is the largest a tile hands on whole).  Sums
+// that are kept in 32 bits are exact modulo 2^32 whatever the total: 2^32
+// divides 2^62.  A tile whose aggregate is 0 still publishes a non-zero
+// granule -- the flag shares the word -- so it counts as arrived.
 #pragma once
 #include "common.hpp"
 

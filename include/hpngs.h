@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 12
+#define HPN_ABI_VERSION 13
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -350,6 +350,17 @@ int hpn_fastq_uniq_write(hpn_ctx *ctx, int which_output, int mate, uint64_t offs
 /* The stable radix sort behind it on its own: n < 2^31 pairs, ascending by key, equal keys in their given order.
  * keys and vals: host or device pointers, sorted in place. */
 int hpn_sort_pairs_u64(hpn_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n);
+/* hpn_sort_pairs_u64 by the key bits [begin_bit, end_bit) only (0 <= begin_bit <= end_bit <= 64); pairs equal in those bits
+ * keep their given order.  The keys come back whole, not masked. */
+int hpn_sort_pairs_u64_bits(hpn_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n, int begin_bit, int end_bit);
+/* ... by the bytes of the key whose bit is set in digits (bit d: key bits [8d, 8d+8)), digits < 256. */
+int hpn_sort_pairs_u64_digits(hpn_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n, uint32_t digits);
+/* The prefix scan behind the families on its own: out[i] = in[0] + ... + in[i-1] for i in 0..n (n + 1 entries; n = 0 writes
+ * out[0] = 0 and takes in == NULL).  (in_bits, out_bits) is one of (32,32), (32,64), (64,64); a 32-bit out holds the sum
+ * modulo 2^32, and the total of a 64-bit one must stay below 2^62.  Host or device pointers; in and out must not overlap.
+ * n < 2^31.  All four: HPN_E_ARG for what is outside the above, HPN_E_DOMAIN at n >= 2^31, HPN_E_STATE while a
+ * hpn_fastq_uniq session is collecting text (they run in its work space). */
+int hpn_excl_scan(hpn_ctx *ctx, const void *in, int in_bits, void *out, int out_bits, uint64_t n);
 
 /* ---- gzfastq_uniqQ.c: one group per distinct sequence, every copy's quality line kept ---------------------
  * The reads of one stream are collapsed by their sequence like hpn_fastq_uniq_* collapses them, framed by the same
