@@ -169,6 +169,16 @@ class BaiResult(C.Structure):
                 ("bad_tid", C.c_int32), ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("n_ref", C.c_uint32)]
 
 
+class BamSortInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
+                ("reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BamSortResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("payload_bytes", C.c_uint64), ("fresh_mem", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32),
+                ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("sort_bits", C.c_uint32)]
+
+
 class GzInfo(C.Structure):
     _fields_ = [("n_bytes", C.c_uint64), ("end_bit", C.c_uint64), ("status", C.c_uint32), ("bad_chunk", C.c_uint32),
                 ("final_chunk", C.c_uint32), ("reserved", C.c_uint32)]
@@ -291,6 +301,15 @@ SYMBOLS = [
     ("hpn_bam_bai_add_raw_dev", _int, [_vp, _vp, _vp, _u64, _vp, _int, _u64, C.POINTER(BaiInfo)]),
     ("hpn_bam_bai_finish", _int, [_vp, C.POINTER(BaiResult)]),
     ("hpn_bam_bai_read", _int, [_vp, _vp, _vp, _vp]),
+    ("hpn_bam_sort_begin", _int, [_vp]),
+    ("hpn_bam_sort_add_raw_dev", _int, [_vp, _vp, C.POINTER(BamSortInfo)]),
+    ("hpn_bam_sort_finish", _int, [_vp, C.POINTER(BamSortResult)]),
+    ("hpn_bam_sort_order", _int, [_vp, _vp, _u64]),
+    ("hpn_bam_sort_sizes", _int, [_vp, _vp, _u64]),
+    ("hpn_bam_sort_emit", _int, [_vp, _u64, _u64, _int, C.POINTER(SplitInfo)]),
+    ("hpn_bam_sort_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_bam_sort_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_sort_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_depth_begin", _int, [_vp, _i32, _u32, _u32]),
     ("hpn_depth_begin_w", _int, [_vp, _i32, _u32, _u32, _u32]),
     ("hpn_depth_progress", _int, [_vp, C.POINTER(_u64)]),
@@ -337,7 +356,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 13:
+    if L.hpn_abi_version() != 14:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

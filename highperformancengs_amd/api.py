@@ -813,6 +813,61 @@ class Context:
                                          _ptr(windows) if res.n_windows else None), "hpn_bam_bai_read")
         return res, targets, chunks, windows
 
+    # ---- samtools sort: a BAM in coordinate order (hpn_bam_sort_*) ----
+    def bam_sort_begin(self):
+        self._ck(self.L.hpn_bam_sort_begin(self.h), "hpn_bam_sort_begin")
+
+    def bam_sort_add_raw_dev(self, d_raw):
+        """The batch hpn_bam_raw_index_dev indexed last goes into the session's record store (d_raw None: no records) -> BamSortInfo."""
+        info = _lib.BamSortInfo()
+        self._ck(self.L.hpn_bam_sort_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), "hpn_bam_sort_add_raw_dev")
+        return info
+
+    def bam_sort_finish(self):
+        """Sorts -> BamSortResult (n_records, payload_bytes, fresh_mem, the first record outside the domain, sort_bits)."""
+        res = _lib.BamSortResult()
+        self._ck(self.L.hpn_bam_sort_finish(self.h, C.byref(res)), "hpn_bam_sort_finish")
+        return res
+
+    def bam_sort_order(self, n):
+        """order[j]: the input ordinal of the j-th record of the output."""
+        out = np.zeros(int(n), np.uint32)
+        self._ck(self.L.hpn_bam_sort_order(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_sort_order")
+        return out
+
+    def bam_sort_sizes(self, n):
+        """sizes[i]: 4 + block_size of input record i."""
+        out = np.zeros(int(n), np.uint32)
+        self._ck(self.L.hpn_bam_sort_sizes(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_sort_sizes")
+        return out
+
+    def bam_sort_emit(self, first_record, max_records, last=False):
+        """The next slice of the sorted records: gathered, cut, every closed block with its CRC-32 -> SplitInfo."""
+        info = _lib.SplitInfo()
+        self._ck(self.L.hpn_bam_sort_emit(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), "hpn_bam_sort_emit")
+        return info
+
+    def bam_sort_blocks(self, n):
+        """The n closed blocks of the last bam_sort_emit -> list of SplitBlock (off, len, crc, tid)."""
+        out = (_lib.SplitBlock * max(int(n), 1))()
+        got = C.c_uint64(0)
+        self._ck(self.L.hpn_bam_sort_blocks(self.h, 0, out, int(n), C.byref(got)), "hpn_bam_sort_blocks")
+        return out[:got.value]
+
+    def bam_sort_payload(self):
+        """The payload buffer of the last bam_sort_emit up to the end of its last closed block, copied to the host."""
+        return self._split_bytes(self.L.hpn_bam_sort_payload_dev, "hpn_bam_sort_payload_dev")
+
+    def bam_sort_payload_dev(self):
+        """-> (device address, bytes) of the same, for callers that look at the buffer where it lies."""
+        p, n = C.c_void_p(0), C.c_uint64(0)
+        self._ck(self.L.hpn_bam_sort_payload_dev(self.h, C.byref(p), C.byref(n)), "hpn_bam_sort_payload_dev")
+        return p.value or 0, n.value
+
+    def bam_sort_stored(self):
+        """The closed blocks of the last bam_sort_emit framed as stored BGZF blocks (level 0), copied to the host."""
+        return self._split_bytes(self.L.hpn_bam_sort_stored_dev, "hpn_bam_sort_stored_dev")
+
     # ---- collectives / synthetic -----------------------------------------
     def comm_init(self, rank, n_ranks, unique_id: bytes):
         buf = (C.c_uint8 * _lib.UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

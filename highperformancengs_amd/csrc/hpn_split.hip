@@ -8,26 +8,19 @@
 
 #include <vector>
 
-#include "hpn_ctx.hpp"
+#include "hpn_cuts.hpp"
 
 namespace hpn {
-// kernels/bam_split.hip
+// kernels/bam_split.hip (the cuts, the block list and the stored framing: hpn_cuts.hpp)
 hipError_t launch_split_keys(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, int32_t n_ref, uint64_t base, uint32_t fill,
                              uint32_t open_key, const void *prev, void *next, u64 *Q, uint32_t *key, u64 *counts, u64 *info, hipStream_t st);
-uint32_t split_tiles(uint64_t m);
-hipError_t launch_split_cuts(const u64 *Q, const uint32_t *key, uint64_t m, int32_t n_ref, uint32_t *a, uint32_t *b, uint32_t *c, uint32_t *mark,
-                             u64 *tile_sum, u64 *info, hipStream_t st);
-hipError_t launch_split_emit(const u64 *Q, const uint32_t *key, const uint32_t *next, const uint32_t *mark, uint64_t m, int32_t n_ref,
-                             const u64 *tile_base, void *out, uint64_t n_out, hipStream_t st);
-hipError_t launch_split_stored(const uint8_t *pay, const void *specs, uint32_t n, uint8_t *img, hipStream_t st);
 }  // namespace hpn
 
 using namespace hpn;
 
 namespace {
-constexpr uint32_t kFull = 0xff00;
-constexpr uint32_t kNoKey = 0xfffffffeu;
-typedef hpn_stored_span StoredSpec;      // (kernels/bam_split.hip reads the same layout)
+constexpr uint32_t kFull = kCutFull;
+constexpr uint32_t kNoKey = kCutNoKey;
 }  // namespace
 
 struct hpn_split_state : FamilyState {
@@ -35,7 +28,8 @@ struct hpn_split_state : FamilyState {
     bool open = false, dead = false, ended = false;
     int32_t n_ref = 0;
     bool level0 = false;
-    Scratch Q, key, ja, jb, jc, mark, tiles, blocks, pay, img, keep, specs, counts, state, info;
+    Scratch Q, key, pay, keep, counts, state, info;
+    CutWork cw;
     int turn = 0;                    // which of the two carried states the next batch reads
     uint64_t records = 0, n_blocks = 0;
     uint32_t fill = 0;               // bytes of the open block (in `keep`)
@@ -91,9 +85,7 @@ int hpn_bam_split_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, int last, hpn_sp
     const uint64_t m = n + 1;
     int rc;
     if ((rc = scratch_reserve(c, u->Q, (m + 1) * sizeof(u64))) != HPN_OK || (rc = scratch_reserve(c, u->key, (m + 1) * sizeof(uint32_t))) != HPN_OK ||
-        (rc = scratch_reserve(c, u->ja, (m + 1) * sizeof(uint32_t))) != HPN_OK || (rc = scratch_reserve(c, u->jb, (m + 1) * sizeof(uint32_t))) != HPN_OK ||
-        (rc = scratch_reserve(c, u->jc, (m + 1) * sizeof(uint32_t))) != HPN_OK || (rc = scratch_reserve(c, u->mark, (m + 1) * sizeof(uint32_t))) != HPN_OK ||
-        (rc = scratch_reserve(c, u->tiles, ((size_t)split_tiles(m) + 1) * sizeof(u64))) != HPN_OK)
+        (rc = cut_reserve(c, u->cw, m)) != HPN_OK)
         return rc;
     const u64 init[4] = {~0ull, 0, 0, 0};
     HPN_HIP(c, hipMemcpyAsync(u->info.p, init, sizeof init, hipMemcpyHostToDevice, c->stream));
@@ -125,56 +117,13 @@ int hpn_bam_split_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, int last, hpn_sp
     if ((rc = scratch_reserve(c, u->pay, total + 64)) != HPN_OK) return rc;
     if (u->fill) HPN_HIP(c, hipMemcpyAsync(u->pay.p, u->keep.p, u->fill, hipMemcpyDeviceToDevice, c->stream));
     if (rec_bytes) HPN_HIP(c, hipMemcpyAsync((uint8_t *)u->pay.p + u->fill, d_raw + h[1], rec_bytes, hipMemcpyDeviceToDevice, c->stream));
-    HPN_HIP(c, launch_split_cuts((const u64 *)u->Q.p, (const uint32_t *)u->key.p, m, u->n_ref, (uint32_t *)u->ja.p, (uint32_t *)u->jb.p,
-                                 (uint32_t *)u->jc.p, (uint32_t *)u->mark.p, (u64 *)u->tiles.p, (u64 *)u->info.p, c->stream));
-    u64 nb = 0;
-    HPN_HIP(c, hipMemcpyAsync(&nb, (const u64 *)u->info.p + 3, sizeof nb, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (nb > total / 32 + 2) return fail(c, HPN_E_HIP, "hpn_bam_split: %llu blocks out of %llu bytes", (unsigned long long)nb, (unsigned long long)total);
-    u->list.resize(nb);
-    if (nb) {
-        if ((rc = scratch_reserve(c, u->blocks, nb * sizeof(hpn_split_block))) != HPN_OK) return rc;
-        HPN_HIP(c, launch_split_emit((const u64 *)u->Q.p, (const uint32_t *)u->key.p, (const uint32_t *)u->ja.p, (const uint32_t *)u->mark.p, m,
-                                     u->n_ref, (const u64 *)u->tiles.p, u->blocks.p, nb, c->stream));
-        HPN_HIP(c, hipMemcpyAsync(u->list.data(), u->blocks.p, nb * sizeof(hpn_split_block), hipMemcpyDeviceToHost, c->stream));
-        HPN_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    for (const hpn_split_block &b : u->list)          // (what the host copies by must lie inside the payload)
-        if (b.len == 0 || b.len > kFull || b.off > total || b.len > total - b.off)
-            return fail(c, HPN_E_HIP, "hpn_bam_split: a block of %u bytes at %llu of %llu", b.len, (unsigned long long)b.off, (unsigned long long)total);
+    if ((rc = cut_blocks(c, u->cw, (const u64 *)u->Q.p, (const uint32_t *)u->key.p, m, u->n_ref, (u64 *)u->info.p, total, u->list, "hpn_bam_split")) != HPN_OK) return rc;
     // the last block stays open while its target may go on
-    u->fill = 0, u->open_tid = -1;
-    if (!last && nb) {
-        const hpn_split_block &b = u->list.back();
-        if (b.off + b.len == total && b.len < kFull) {
-            HPN_HIP(c, hipMemcpyAsync(u->keep.p, (const uint8_t *)u->pay.p + b.off, b.len, hipMemcpyDeviceToDevice, c->stream));
-            u->fill = b.len, u->open_tid = b.tid;
-            u->list.pop_back();
-        }
-    }
+    if ((rc = carry_open(c, u->keep, (const uint8_t *)u->pay.p, u->list, total, last != 0, &u->fill, &u->open_tid)) != HPN_OK) return rc;
     if (last) u->ended = true;
     const size_t nc = u->list.size();
-    if (nc) {
-        std::vector<hpn_span> spans(nc);
-        std::vector<uint32_t> crcs(nc);
-        for (size_t k = 0; k < nc; ++k) spans[k] = hpn_span{u->list[k].off, u->list[k].len};
-        if ((rc = hpn_crc32_dev(c, (const uint8_t *)u->pay.p, spans.data(), (uint32_t)nc, crcs.data())) != HPN_OK) return rc;
-        for (size_t k = 0; k < nc; ++k) u->list[k].crc = crcs[k];
-        u->payload_bytes = u->list.back().off + u->list.back().len;
-        if (u->level0) {
-            std::vector<StoredSpec> specs(nc);
-            uint64_t at = 0;
-            for (size_t k = 0; k < nc; ++k) {
-                specs[k] = StoredSpec{u->list[k].off, at, u->list[k].len, u->list[k].crc};
-                at += (uint64_t)u->list[k].len + 31;
-            }
-            if ((rc = scratch_reserve(c, u->specs, nc * sizeof(StoredSpec))) != HPN_OK || (rc = scratch_reserve(c, u->img, at + 64)) != HPN_OK) return rc;
-            HPN_HIP(c, hipMemcpyAsync(u->specs.p, specs.data(), nc * sizeof(StoredSpec), hipMemcpyHostToDevice, c->stream));
-            HPN_HIP(c, launch_split_stored((const uint8_t *)u->pay.p, u->specs.p, (uint32_t)nc, (uint8_t *)u->img.p, c->stream));
-            u->stored_bytes = at;
-        }
-        info->tid_first = u->list.front().tid, info->tid_last = u->list.back().tid;
-    }
+    if ((rc = close_blocks(c, u->cw, (const uint8_t *)u->pay.p, u->list, u->level0, &u->payload_bytes, &u->stored_bytes)) != HPN_OK) return rc;
+    if (nc) info->tid_first = u->list.front().tid, info->tid_last = u->list.back().tid;
     HPN_HIP(c, hipStreamSynchronize(c->stream));
     u->n_blocks += nc;
     info->n_blocks = nc, info->payload_bytes = u->payload_bytes, info->stored_bytes = u->stored_bytes, info->open_bytes = u->fill;
@@ -189,10 +138,10 @@ int hpn_bgzf_stored_dev(hpn_ctx *c, const uint8_t *d_data, const hpn_stored_span
     if (!n_spans) return HPN_OK;
     HPN_HIP(c, hipSetDevice(c->device));
     hpn_split_state *u = state_make<hpn_split_state>(c);
-    const int rc = scratch_reserve(c, u->specs, (size_t)n_spans * sizeof(StoredSpec));
+    const int rc = scratch_reserve(c, u->cw.specs, (size_t)n_spans * sizeof(StoredSpec));
     if (rc != HPN_OK) return rc;
-    HPN_HIP(c, hipMemcpyAsync(u->specs.p, spans, (size_t)n_spans * sizeof(StoredSpec), hipMemcpyHostToDevice, c->stream));
-    HPN_HIP(c, launch_split_stored(d_data, u->specs.p, n_spans, d_image, c->stream));
+    HPN_HIP(c, hipMemcpyAsync(u->cw.specs.p, spans, (size_t)n_spans * sizeof(StoredSpec), hipMemcpyHostToDevice, c->stream));
+    HPN_HIP(c, launch_split_stored(d_data, u->cw.specs.p, n_spans, d_image, c->stream));
     HPN_HIP(c, hipStreamSynchronize(c->stream));
     return HPN_OK;
 }
@@ -226,7 +175,7 @@ int hpn_bam_split_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_by
     hpn_split_state *u = state<hpn_split_state>(c);
     if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_stored_dev before hpn_bam_split_begin");
     if (!u->level0) return fail(c, HPN_E_STATE, "hpn_bam_split_stored_dev: the session was not begun with level0");
-    *d_image = (const uint8_t *)u->img.p, *n_bytes = u->stored_bytes;
+    *d_image = (const uint8_t *)u->cw.img.p, *n_bytes = u->stored_bytes;
     return HPN_OK;
 }
 

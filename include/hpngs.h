@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 13
+#define HPN_ABI_VERSION 14
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -1069,6 +1069,54 @@ int hpn_bam_bai_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw, const hpn_bgzf_b
                             int last, uint64_t end_voffset, hpn_bai_info *info);
 int hpn_bam_bai_finish(hpn_ctx *ctx, hpn_bai_result *res);
 int hpn_bam_bai_read(hpn_ctx *ctx, hpn_bai_target *targets /* [n_ref] */, hpn_bai_chunk *chunks /* [n_chunks] */, uint64_t *windows /* [n_windows] */);
+
+/* ---- samtools sort: a BAM in coordinate order --------------------------------------------------
+ * bam_sort.c (samtools-0.1.19) for the order by coordinate: the key of bam1_lt, (uint64_t)refID << 32 | (pos + 1) << 1 | strand
+ * (strand: flag 0x10), sorted stably -- records of one key keep their input order, refID -1 goes last, any other refID sorts by
+ * its unsigned value --, and the sorted records cut into BGZF blocks by bam_write1's rule (see hpn_bam_split_*).
+ * (docs/kernels/bam_sort.md)
+ *   hpn_bam_sort_begin()
+ *   per batch: hpn_bam_raw_index_dev(...), then hpn_bam_sort_add_raw_dev(d_raw, &info): the batch's records are copied into
+ *              the session's record store on the device (d_raw may be reused afterwards); d_raw NULL: no records
+ *   hpn_bam_sort_finish(&res)             sorts; res.payload_bytes: the records' bytes, res.fresh_mem: what bam_sort_core_ext
+ *                                         would have counted if every record had come into a fresh slot, the sum of
+ *                                         72 + kroundup32(block_size - 32) -- below max_mem the reference sorts in one block
+ *   hpn_bam_sort_order(order, n)          order[j]: the input ordinal of the j-th record of the output (n = res.n_records)
+ *   hpn_bam_sort_sizes(sizes, n)          sizes[i] = 4 + block_size of input record i (the reference's chunk accounting)
+ *   hpn_bam_sort_emit(first_record, max_records, last, &info)
+ *              the next slice of the output, records [first_record, first_record + max_records) of the sorted order (slices
+ *              are taken front to back: first_record is where the slice before ended): gathered behind the bytes of the block
+ *              the slice before left open, cut, every closed block with its CRC-32.  The last block of a slice stays open
+ *              unless `last` (which must come with the slice that takes the last record, or with an empty one behind it).
+ *              info as in hpn_bam_split_add_raw_dev; every block's tid is 0.
+ *   hpn_bam_sort_blocks / _payload_dev / _stored_dev    the slice's closed blocks, the payload buffer they point into, and
+ *              (made when asked for) the blocks framed as stored BGZF blocks; valid until the next hpn_bam_sort_* call.
+ * Domain: -1 <= pos <= 2^30 - 2 for every record (outside it bam1_lt's key and the key of the reference's merge step
+ * disagree, and the order depends on the reference's chunking) and fewer than 2^31 records.  The first record outside it is
+ * reported -- bad_record (ordinal, -1: none), bad_tid, bad_pos, reason (1 pos below -1, 2 pos above 2^30 - 2, 3 the 2^31-th
+ * record) -- and nothing is sorted: the caller sorts on the host (csrc/host/bam_sort_host.hpp).  Synchronous. */
+typedef struct hpn_bamsort_info {
+    uint64_t n_records;      /* records of this batch */
+    uint64_t store_bytes;    /* bytes the record store holds after this call */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, reserved;
+} hpn_bamsort_info;
+typedef struct hpn_bamsort_result {
+    uint64_t n_records, payload_bytes, fresh_mem;
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, sort_bits; /* sort_bits: the key bits [0, sort_bits) the radix sort ran over */
+} hpn_bamsort_result;
+int hpn_bam_sort_begin(hpn_ctx *ctx);
+int hpn_bam_sort_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw, hpn_bamsort_info *info);
+int hpn_bam_sort_finish(hpn_ctx *ctx, hpn_bamsort_result *res);
+int hpn_bam_sort_order(hpn_ctx *ctx, uint32_t *order, uint64_t n);
+int hpn_bam_sort_sizes(hpn_ctx *ctx, uint32_t *sizes, uint64_t n);
+int hpn_bam_sort_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info);
+int hpn_bam_sort_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
+int hpn_bam_sort_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
+int hpn_bam_sort_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
 
 /* ---- multi-GPU reduction of count vectors -----------------------------------
  * One RCCL communicator per context; `unique_id` is the 128-byte ncclUniqueId
