@@ -179,6 +179,24 @@ class BamSortResult(C.Structure):
                 ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("sort_bits", C.c_uint32)]
 
 
+class RmdupInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
+                ("reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RmdupResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_out", C.c_uint64), ("payload_bytes", C.c_uint64), ("n_heads", C.c_uint64), ("bad_record", C.c_int64),
+                ("bad_tid", C.c_int32), ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("n_libs", C.c_uint32), ("n_ref", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RmdupLib(C.Structure):
+    _fields_ = [("checked", C.c_uint64), ("removed", C.c_uint64), ("first", C.c_int64)]
+
+
+class RmdupTarget(C.Structure):
+    _fields_ = [("unmatched", C.c_uint64), ("has_records", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class GzInfo(C.Structure):
     _fields_ = [("n_bytes", C.c_uint64), ("end_bit", C.c_uint64), ("status", C.c_uint32), ("bad_chunk", C.c_uint32),
                 ("final_chunk", C.c_uint32), ("reserved", C.c_uint32)]
@@ -310,6 +328,15 @@ SYMBOLS = [
     ("hpn_bam_sort_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_bam_sort_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_sort_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_rmdup_begin", _int, [_vp, _i32, _u32, _vp, _vp, _u32]),
+    ("hpn_bam_rmdup_add_raw_dev", _int, [_vp, _vp, C.POINTER(RmdupInfo)]),
+    ("hpn_bam_rmdup_finish", _int, [_vp, C.POINTER(RmdupResult)]),
+    ("hpn_bam_rmdup_counts", _int, [_vp, _vp, _vp]),
+    ("hpn_bam_rmdup_order", _int, [_vp, _vp, _u64]),
+    ("hpn_bam_rmdup_emit", _int, [_vp, _u64, _u64, _int, C.POINTER(SplitInfo)]),
+    ("hpn_bam_rmdup_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_bam_rmdup_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_rmdup_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_depth_begin", _int, [_vp, _i32, _u32, _u32]),
     ("hpn_depth_begin_w", _int, [_vp, _i32, _u32, _u32, _u32]),
     ("hpn_depth_progress", _int, [_vp, C.POINTER(_u64)]),
@@ -356,7 +383,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 14:
+    if L.hpn_abi_version() != 15:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -868,6 +868,69 @@ class Context:
         """The closed blocks of the last bam_sort_emit framed as stored BGZF blocks (level 0), copied to the host."""
         return self._split_bytes(self.L.hpn_bam_sort_stored_dev, "hpn_bam_sort_stored_dev")
 
+    # ---- samtools rmdup: duplicates of a coordinate-sorted BAM removed (hpn_bam_rmdup_*) ----
+    def bam_rmdup_begin(self, n_ref, ids=(), lib_of_id=(), n_libs=1):
+        """ids: the header's @RG IDs (bytes), lib_of_id: each one's library in [1, n_libs); library 0: no RG, an unknown ID, no LB."""
+        arr = (C.c_char_p * max(len(ids), 1))(*[bytes(i) for i in ids])
+        lib = np.ascontiguousarray(lib_of_id, np.uint32)
+        assert len(lib) == len(ids)
+        self._ck(self.L.hpn_bam_rmdup_begin(self.h, int(n_ref), len(ids), C.cast(arr, C.c_void_p) if len(ids) else None, _ptr(lib) if len(ids) else None,
+                                            int(n_libs)), "hpn_bam_rmdup_begin")
+        self._rmdup_shape = (int(n_ref), int(n_libs))
+
+    def bam_rmdup_add_raw_dev(self, d_raw):
+        """The batch hpn_bam_raw_index_dev indexed last is classified and goes into the session's record store -> RmdupInfo."""
+        info = _lib.RmdupInfo()
+        self._ck(self.L.hpn_bam_rmdup_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), "hpn_bam_rmdup_add_raw_dev")
+        return info
+
+    def bam_rmdup_finish(self):
+        """Decides -> RmdupResult (n_records, n_out, payload_bytes, n_heads, the first record outside the domain)."""
+        res = _lib.RmdupResult()
+        self._ck(self.L.hpn_bam_rmdup_finish(self.h, C.byref(res)), "hpn_bam_rmdup_finish")
+        return res
+
+    def bam_rmdup_counts(self):
+        """-> ([(checked, removed, first head's ordinal or -1)] per library, [(has records, unmatched names)] per target and, last,
+        for the unplaced records behind them)"""
+        n_ref, n_libs = self._rmdup_shape
+        libs, targets = (_lib.RmdupLib * n_libs)(), (_lib.RmdupTarget * (n_ref + 1))()
+        self._ck(self.L.hpn_bam_rmdup_counts(self.h, C.cast(libs, C.c_void_p), C.cast(targets, C.c_void_p)), "hpn_bam_rmdup_counts")
+        return [(l.checked, l.removed, l.first) for l in libs], [(bool(t.has_records), t.unmatched) for t in targets]
+
+    def bam_rmdup_order(self, n):
+        """order[j]: the input ordinal of the j-th record of the output."""
+        out = np.zeros(int(n), np.uint32)
+        self._ck(self.L.hpn_bam_rmdup_order(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_rmdup_order")
+        return out
+
+    def bam_rmdup_emit(self, first_record, max_records, last=False):
+        """The next slice of the surviving records: gathered, cut, every closed block with its CRC-32 -> SplitInfo."""
+        info = _lib.SplitInfo()
+        self._ck(self.L.hpn_bam_rmdup_emit(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), "hpn_bam_rmdup_emit")
+        return info
+
+    def bam_rmdup_blocks(self, n):
+        """The n closed blocks of the last bam_rmdup_emit -> list of SplitBlock (off, len, crc, tid)."""
+        out = (_lib.SplitBlock * max(int(n), 1))()
+        got = C.c_uint64(0)
+        self._ck(self.L.hpn_bam_rmdup_blocks(self.h, 0, out, int(n), C.byref(got)), "hpn_bam_rmdup_blocks")
+        return out[:got.value]
+
+    def bam_rmdup_payload(self):
+        """The payload buffer of the last bam_rmdup_emit up to the end of its last closed block, copied to the host."""
+        return self._split_bytes(self.L.hpn_bam_rmdup_payload_dev, "hpn_bam_rmdup_payload_dev")
+
+    def bam_rmdup_payload_dev(self):
+        """-> (device address, bytes) of the same, for callers that look at the buffer where it lies."""
+        p, n = C.c_void_p(0), C.c_uint64(0)
+        self._ck(self.L.hpn_bam_rmdup_payload_dev(self.h, C.byref(p), C.byref(n)), "hpn_bam_rmdup_payload_dev")
+        return p.value or 0, n.value
+
+    def bam_rmdup_stored(self):
+        """The closed blocks of the last bam_rmdup_emit framed as stored BGZF blocks (level 0), copied to the host."""
+        return self._split_bytes(self.L.hpn_bam_rmdup_stored_dev, "hpn_bam_rmdup_stored_dev")
+
     # ---- collectives / synthetic -----------------------------------------
     def comm_init(self, rank, n_ranks, unique_id: bytes):
         buf = (C.c_uint8 * _lib.UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

@@ -1,0 +1,202 @@
+// bam_rmdup -- drop-in for `samtools rmdup` of the samtools-0.1.19 the reference vendors (bam_rmdup.c: bam_rmdup ->
+// bam_rmdup_core / bam_rmdupse_core): a coordinate-sorted BAM without its PCR duplicates, byte for byte samtools', with its
+// messages and status; the decisions, the gather of the survivors, the BGZF cuts and the CRC-32 of every block made on MI355X
+// through libhpngs.
+//
+//   bam_rmdup [-sS] <input.srt.bam> <output.bam>
+//
+// The file is inflated and its records are indexed on the device as bam_sort's are; hpn_bam_rmdup_* classifies every record,
+// keeps the records in a store on the device and hands the output back slice by slice.  -s and -S, a header that is not parsed
+// in silence, a file that is not sorted or begins with unplaced records, an RG tag that is no string, aux fields outside the
+// format, an inconsistent pair, a damaged or truncated file and a working set beyond the device's memory go to the sequential
+// host route (host/bam_rmdup_host.hpp); HPN_BAM_GPU=0 selects it from the start.  HPN_TIMING=1 says which route ran.
+#include <sys/stat.h>
+
+#include <algorithm>
+
+#include "../host/bam_gpu.hpp"
+#include "../host/bam_rmdup_host.hpp"
+#include "../host/report.hpp"
+
+using namespace hpn;
+
+#ifdef HPN_TEST_HOOKS
+static const uint64_t kSliceRecords = 1000;        // (the test-hooks build: the open block is carried over many slices)
+#else
+static const uint64_t kSliceRecords = 1u << 22;    // ~1 GB of payload per slice at 250 bytes a record
+#endif
+
+// 0 the output is written, 1 not for the device (the host route starts over; nothing has been said, no output is left)
+static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
+{
+    std::string said;
+    bamsort::Header hdr;
+    {   // the header on the host: its blocks are the writer's first, its @RG lines the device's table
+        FILE *f = fopen(o.in, "rb");
+        if (!f) return 1;
+        if (!bai::has_eof_marker(f)) said += "[bam_header_read] EOF marker is absent. The input is probably truncated.\n";
+        bai::BgzfSeq z(f);
+        const int hr = bamsort::read_header(z, hdr);
+        fclose(f);
+        if (hr != 0) return 1;
+    }
+    std::map<std::string, std::string> tbl;
+    if (!rmdup::id_table(hdr.text, tbl)) return 1;
+    std::vector<std::string> lib_name(1, "\t");       // library 0: no RG, an unknown ID, no LB
+    std::vector<const char *> ids;
+    std::vector<uint32_t> lib_of_id;
+    for (const auto &kv : tbl) {
+        if (kv.first.find('\0') != std::string::npos) return 1;
+        size_t l = std::find(lib_name.begin() + 1, lib_name.end(), kv.second) - lib_name.begin();
+        if (kv.second == "\t") l = 0;
+        if (l == lib_name.size()) lib_name.push_back(kv.second);
+        ids.push_back(kv.first.c_str()), lib_of_id.push_back((uint32_t)l);
+    }
+    BgzfGpuStream bam;
+    BamHeader parsed;
+    if (!bam.open(ctx, o.in, parsed)) return 1;
+    bam.start();
+    int rc = hpn_bam_rmdup_begin(ctx, (int32_t)hdr.name.size(), (uint32_t)ids.size(), ids.data(), lib_of_id.data(), (uint32_t)lib_name.size());
+    if (rc == HPN_E_ARG || rc == HPN_E_NOMEM) return 1;       // (more IDs than the table takes)
+    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_begin");
+    double t_ingest = 0, t_store = 0, t_decide = 0, t_emit = 0, t_copy = 0, t_hand = 0, t0;
+    uint64_t n_batches = 0, n_blocks = 0;
+    bool empty_seen = false;
+    auto outside = [&](long long rec, int tid, int pos, unsigned reason) {
+        if (timing) fprintf(stderr, "[hpn] bam_rmdup: record %lld (refID %d, pos %d) is outside the device's domain (reason %u)\n", rec, tid, pos, reason);
+        return 1;
+    };
+    for (;;) {
+        hpn_raw_info info;
+        t0 = wall_s();
+        const int r = bam.next(&info);
+        t_ingest += wall_s() - t0;
+        if (r < 0) return 1;
+        if (r == 0) break;
+        const BgzfDevice &dev = bam.device();
+        if (!dev.n_blocks()) continue;
+        // a block of no bytes ends the stream for samtools' reader: only the file's last block may be one
+        if (empty_seen || dev.empty_blocks() > 1 || (dev.empty_blocks() == 1 && !dev.last_block_empty())) return 1;
+        empty_seen = dev.empty_blocks() != 0;
+        if (!info.n_records) continue;
+        hpn_rmdup_info ri;
+        t0 = wall_s();
+        rc = hpn_bam_rmdup_add_raw_dev(ctx, bam.d_raw(), &ri);
+        if (rc == HPN_E_NOMEM) return 1;                   // the working set does not fit the device
+        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_add_raw_dev");
+        t_store += wall_s() - t0, ++n_batches;
+        if (ri.bad_record >= 0) return outside((long long)ri.bad_record, ri.bad_tid, ri.bad_pos, ri.reason);
+    }
+    hpn_rmdup_result res;
+    t0 = wall_s();
+    rc = hpn_bam_rmdup_finish(ctx, &res);
+    if (rc == HPN_E_NOMEM) return 1;
+    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_finish");
+    if (res.bad_record >= 0) return outside((long long)res.bad_record, res.bad_tid, res.bad_pos, res.reason);
+    std::vector<hpn_rmdup_lib> libs(lib_name.size());
+    std::vector<hpn_rmdup_target> targets(hdr.name.size() + 1);
+    if ((rc = hpn_bam_rmdup_counts(ctx, libs.data(), targets.data())) != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_counts");
+    t_decide = wall_s() - t0;
+    const std::vector<uint8_t> head = hdr.bytes();
+    std::vector<uint8_t> head_blocks;
+    if (!bgzf_plain_blocks(head.data(), head.size(), -1, head_blocks)) return 1;
+    BgzfWriter writer(-1);
+    bool created = false;
+    auto give_up = [&]() {      // the output so far goes; the host route makes it again
+        if (created) {
+            writer.abandon();
+            unlink(o.out);
+        }
+        return 1;
+    };
+    std::vector<hpn_split_block> blocks;
+    std::vector<uint8_t> bytes;
+    for (uint64_t first = 0;;) {
+        const uint64_t cnt = res.n_out - first < kSliceRecords ? res.n_out - first : kSliceRecords;
+        const bool last = first + cnt == res.n_out;
+        hpn_split_info si;
+        t0 = wall_s();
+        rc = hpn_bam_rmdup_emit(ctx, first, cnt, last ? 1 : 0, &si);
+        if (rc == HPN_E_NOMEM) return give_up();
+        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_emit");
+        t_emit += wall_s() - t0, t0 = wall_s();
+        uint64_t nb = 0, n = 0;
+        const uint8_t *d = nullptr;
+        blocks.resize(si.n_blocks);
+        if ((rc = hpn_bam_rmdup_blocks(ctx, 0, blocks.data(), blocks.size(), &nb)) != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_blocks");
+        if ((rc = hpn_bam_rmdup_payload_dev(ctx, &d, &n)) != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_payload_dev");
+        bytes.resize(n);
+        if (n && ((rc = hpn_memcpy_d2h(ctx, bytes.data(), d, n)) != HPN_OK || (rc = hpn_ctx_sync(ctx)) != HPN_OK)) die_hpn(ctx, rc, "hpn_memcpy_d2h");
+        t_copy += wall_s() - t0, t0 = wall_s();
+        if (!created) {      // (behind the first slice: everything the device needs has been allocated by now)
+            if (!writer.begin(o.out, head_blocks)) {
+                fputs(said.c_str(), stderr);
+                fputs("[bam_rmdup] fail to read/write input files\n", stderr);
+                leave(1);
+            }
+            created = true;
+        }
+        for (size_t k = 0; k < nb; ++k) writer.add(bytes.data() + blocks[k].off, blocks[k].len, blocks[k].crc, true);
+        n_blocks += nb;
+        t_hand += wall_s() - t0;
+        first += cnt;
+        if (last) break;
+    }
+    if (!writer.finish()) {
+        fprintf(stderr, "[hpn] bam_rmdup: writing %s failed\n", o.out);
+        leave(2);
+    }
+    // the reference's words, now that nothing can send the file to the host any more: per target that has records what the
+    // target before left in the set, then "processing reference"; the same check where the unplaced records begin; the libraries
+    // in the order of khash's buckets, entered as their first heads came
+    fputs(said.c_str(), stderr);
+    uint64_t pending = 0;
+    for (size_t t = 0; t < targets.size(); ++t) {
+        if (!targets[t].has_records) continue;
+        if (pending) fprintf(stderr, "[bam_rmdup_core] %llu unmatched pairs\n", (unsigned long long)pending);
+        if (t < hdr.name.size()) fprintf(stderr, "[bam_rmdup_core] processing reference %s...\n", hdr.name[t].c_str());
+        pending = targets[t].unmatched;
+    }
+    std::vector<std::pair<int64_t, size_t>> by_first;
+    std::map<std::string, rmdup::LibCount> counts;
+    for (size_t l = 0; l < libs.size(); ++l)
+        if (libs[l].first >= 0) {
+            by_first.emplace_back(libs[l].first, l);
+            counts[lib_name[l]].checked = libs[l].checked, counts[lib_name[l]].removed = libs[l].removed;
+        }
+    std::sort(by_first.begin(), by_first.end());
+    std::vector<std::string> seen;
+    for (const auto &f : by_first) seen.push_back(lib_name[f.second]);
+    rmdup::library_lines("bam_rmdup_core", counts, seen);
+    if (timing)
+        fprintf(stderr, "[hpn] bam_rmdup: inflate + record index %.3f s, classify + store %.3f s, groups + names + placement %.3f s, gather + cuts + crc %.3f s, "
+                        "copies to the host %.3f s, handing to the writer %.3f s; %llu batches, %llu records in, %llu heads, %llu records out, %llu blocks; "
+                        "writer: %.3f s deflating (all threads), %.3f s waited for\n",
+                t_ingest, t_store, t_decide, t_emit, t_copy, t_hand, (unsigned long long)n_batches, (unsigned long long)res.n_records,
+                (unsigned long long)res.n_heads, (unsigned long long)res.n_out, (unsigned long long)n_blocks, writer.deflate_seconds(), writer.waited_seconds());
+    return 0;
+}
+
+int main(int argc, char *argv[])
+{
+    bind_before_runtime();
+    stamp("main");
+    rmdup::Options o;
+    if (!rmdup::parse_args(argc, argv, o)) return 1;
+    const bool timing = getenv("HPN_TIMING") != nullptr;
+    if (bam_gpu_enabled() && !o.se && strcmp(o.in, "-") != 0 && strcmp(o.out, "-") != 0 && access(o.in, R_OK) == 0) {
+        hpn_ctx *ctx = open_tool_ctx();
+        stamp("context created");
+        const int r = rmdup_device(ctx, o, timing);
+        if (timing) fprintf(stderr, "[hpn] bam_rmdup: %s\n", r == 0 ? "device route" : "device route abandoned: host route");
+        if (r == 0) {
+            stamp("finished");
+            quick_exit_ok();
+        }
+    } else if (timing) {
+        fprintf(stderr, "[hpn] bam_rmdup: host route\n");
+    }
+    const int status = rmdup::rmdup_on_host(o);
+    stamp("finished");
+    leave(status);
+}

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 14
+#define HPN_ABI_VERSION 15
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -1117,6 +1117,76 @@ int hpn_bam_sort_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records,
 int hpn_bam_sort_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
 int hpn_bam_sort_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
 int hpn_bam_sort_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
+
+/* ---- samtools rmdup: PCR duplicates of a coordinate-sorted BAM removed (pairs) -------------------
+ * bam_rmdup.c (samtools-0.1.19), bam_rmdup_core: among the heads (paired, both mates mapped to one target, isize > 0) of one
+ * (refID, pos, library, isize) the first one with the largest sum of qualities stays and leaves from the place of the group's
+ * first record, behind everything of its (refID, pos) that is written at once; every other head's name goes into a set, and a
+ * tail (isize <= 0) whose name is in the set is dropped.  The survivors are cut into BGZF blocks by bam_write1's rule (see
+ * hpn_bam_split_*).  (docs/kernels/bam_rmdup.md)
+ *   hpn_bam_rmdup_begin(n_ref, n_ids, ids, lib_of_id, n_libs)
+ *              the header's @RG table: ID ids[k] (a C string) belongs to library lib_of_id[k] in [1, n_libs); library 0 is the
+ *              one of records without an RG tag, with an ID the table lacks or whose @RG has no LB (the reference's "\t").
+ *              Libraries are the caller's numbering of the distinct LB strings.
+ *   per batch: hpn_bam_raw_index_dev(...), then hpn_bam_rmdup_add_raw_dev(d_raw, &info): the batch's records are classified and
+ *              copied into the session's record store (d_raw may be reused afterwards); d_raw NULL: no records.  A batch may end
+ *              anywhere: runs, groups and name events are made by _finish from what all batches left.
+ *   hpn_bam_rmdup_finish(&res)            decides; res.n_out records survive, res.payload_bytes their bytes
+ *   hpn_bam_rmdup_counts(libs, targets)   libs[l] (n_libs entries): heads checked and removed of library l and its first head's
+ *                                         ordinal (-1: none; the order of first heads is the reference's insertion order, which
+ *                                         decides the order of its summary lines); targets[t] (n_ref + 1 entries): whether
+ *                                         target t has records and the names left in the set when it ends ("N unmatched
+ *                                         pairs"); targets[n_ref].has_records: unplaced records follow the placed ones
+ *   hpn_bam_rmdup_order(order, n)         order[j]: the input ordinal of the j-th record of the output (n = res.n_out)
+ *   hpn_bam_rmdup_emit / _blocks / _payload_dev / _stored_dev    as hpn_bam_sort_emit and its three readers
+ * Domain: (unsigned refID, pos) never goes backwards, pos >= 0 on every placed record, refID -1 only behind every placed record
+ * and not on the first, every refID inside the header, fewer than 2^31 records; for heads and tails a name that ends with its
+ * only NUL; for heads an RG tag of type Z and aux fields of the format's types that end inside the record; no name inserted into
+ * the set twice.  The first record outside it is reported -- bad_record (ordinal, -1: none), bad_tid, bad_pos, reason
+ * (HPN_RMDUP_*) -- and nothing is decided: the caller follows the reference on the host (csrc/host/bam_rmdup_host.hpp).
+ * Synchronous. */
+#define HPN_RMDUP_TID_BACK 1        /* a refID below the one before (unsigned), or a placed record behind an unplaced one */
+#define HPN_RMDUP_POS_BACK 2        /* a pos below the one before on the same target */
+#define HPN_RMDUP_RECORDS 3         /* the 2^31-th record */
+#define HPN_RMDUP_RG_TYPE 4         /* a head's RG tag is not of type Z */
+#define HPN_RMDUP_AUX 5             /* a head's aux fields: a type outside AcCsSiIfZHB, or a field that ends behind the record */
+#define HPN_RMDUP_NAME 6            /* a head's or tail's name: l_read_name 0, a NUL inside it or none at its end */
+#define HPN_RMDUP_INCONSISTENT 7    /* "inconsistent BAM file for pair": a name inserted into the set while it is in it */
+#define HPN_RMDUP_COLLISION 8       /* two different names with one 64-bit hash */
+#define HPN_RMDUP_FIRST_UNPLACED 9  /* the file begins with refID -1 */
+#define HPN_RMDUP_TID_BEYOND 10     /* a refID the header does not have */
+#define HPN_RMDUP_POS_NEG 11        /* pos below 0 on a placed record */
+#define HPN_RMDUP_FIELDS 12         /* a head's fixed fields lead outside the record */
+typedef struct hpn_rmdup_info {
+    uint64_t n_records;      /* records of this batch */
+    uint64_t store_bytes;    /* bytes the record store holds after this call */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, reserved;
+} hpn_rmdup_info;
+typedef struct hpn_rmdup_result {
+    uint64_t n_records, n_out, payload_bytes, n_heads;
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, n_libs, n_ref, reserved;
+} hpn_rmdup_result;
+typedef struct hpn_rmdup_lib {
+    uint64_t checked, removed;
+    int64_t first;
+} hpn_rmdup_lib;
+typedef struct hpn_rmdup_target {
+    uint64_t unmatched;
+    uint32_t has_records, reserved;
+} hpn_rmdup_target;
+int hpn_bam_rmdup_begin(hpn_ctx *ctx, int32_t n_ref, uint32_t n_ids, const char *const *ids, const uint32_t *lib_of_id, uint32_t n_libs);
+int hpn_bam_rmdup_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw, hpn_rmdup_info *info);
+int hpn_bam_rmdup_finish(hpn_ctx *ctx, hpn_rmdup_result *res);
+int hpn_bam_rmdup_counts(hpn_ctx *ctx, hpn_rmdup_lib *libs /* [n_libs] */, hpn_rmdup_target *targets /* [n_ref + 1] */);
+int hpn_bam_rmdup_order(hpn_ctx *ctx, uint32_t *order, uint64_t n);
+int hpn_bam_rmdup_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info);
+int hpn_bam_rmdup_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
+int hpn_bam_rmdup_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
+int hpn_bam_rmdup_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
 
 /* ---- multi-GPU reduction of count vectors -----------------------------------
  * One RCCL communicator per context; `unique_id` is the 128-byte ncclUniqueId
