@@ -748,27 +748,35 @@ class Context:
 
     def split_blocks(self, n):
         """The n closed blocks of the last split_add_raw_dev -> ctypes array of SplitBlock (off, len, crc, tid)."""
+        return self._last_blocks("hpn_bam_split_blocks", n)
+
+    # what the sessions that write BAM blocks (split, sort, rmdup) answer alike, by the C function's name
+    def _last_blocks(self, name, n):
         out = (_lib.SplitBlock * max(int(n), 1))()
         got = C.c_uint64(0)
-        self._ck(self.L.hpn_bam_split_blocks(self.h, 0, out, int(n), C.byref(got)), "hpn_bam_split_blocks")
+        self._ck(getattr(self.L, name)(self.h, 0, out, int(n), C.byref(got)), name)
         return out[:got.value]
 
-    def _split_bytes(self, fn, name):
+    def _dev_span(self, name):
         p, n = C.c_void_p(0), C.c_uint64(0)
-        self._ck(fn(self.h, C.byref(p), C.byref(n)), name)
-        host = np.zeros(n.value, np.uint8)
-        if n.value:
-            self._ck(self.L.hpn_memcpy_d2h(self.h, _ptr(host), p, n.value), "hpn_memcpy_d2h")
+        self._ck(getattr(self.L, name)(self.h, C.byref(p), C.byref(n)), name)
+        return p.value or 0, n.value
+
+    def _dev_span_bytes(self, name):
+        p, n = self._dev_span(name)
+        host = np.zeros(n, np.uint8)
+        if n:
+            self._ck(self.L.hpn_memcpy_d2h(self.h, _ptr(host), p, n), "hpn_memcpy_d2h")
             self.sync()
         return host.tobytes()
 
     def split_payload(self):
         """The payload buffer of the last call up to the end of its last closed block, copied to the host."""
-        return self._split_bytes(self.L.hpn_bam_split_payload_dev, "hpn_bam_split_payload_dev")
+        return self._dev_span_bytes("hpn_bam_split_payload_dev")
 
     def split_stored(self):
         """The closed blocks of the last call as the device framed them (level 0), copied to the host."""
-        return self._split_bytes(self.L.hpn_bam_split_stored_dev, "hpn_bam_split_stored_dev")
+        return self._dev_span_bytes("hpn_bam_split_stored_dev")
 
     def bgzf_stored_dev(self, d_data, spans, d_image):
         """spans: (off, img_off, len, crc) per block -> each framed as a stored BGZF block of len + 31 bytes at d_image + img_off."""
@@ -849,24 +857,19 @@ class Context:
 
     def bam_sort_blocks(self, n):
         """The n closed blocks of the last bam_sort_emit -> list of SplitBlock (off, len, crc, tid)."""
-        out = (_lib.SplitBlock * max(int(n), 1))()
-        got = C.c_uint64(0)
-        self._ck(self.L.hpn_bam_sort_blocks(self.h, 0, out, int(n), C.byref(got)), "hpn_bam_sort_blocks")
-        return out[:got.value]
+        return self._last_blocks("hpn_bam_sort_blocks", n)
 
     def bam_sort_payload(self):
         """The payload buffer of the last bam_sort_emit up to the end of its last closed block, copied to the host."""
-        return self._split_bytes(self.L.hpn_bam_sort_payload_dev, "hpn_bam_sort_payload_dev")
+        return self._dev_span_bytes("hpn_bam_sort_payload_dev")
 
     def bam_sort_payload_dev(self):
         """-> (device address, bytes) of the same, for callers that look at the buffer where it lies."""
-        p, n = C.c_void_p(0), C.c_uint64(0)
-        self._ck(self.L.hpn_bam_sort_payload_dev(self.h, C.byref(p), C.byref(n)), "hpn_bam_sort_payload_dev")
-        return p.value or 0, n.value
+        return self._dev_span("hpn_bam_sort_payload_dev")
 
     def bam_sort_stored(self):
         """The closed blocks of the last bam_sort_emit framed as stored BGZF blocks (level 0), copied to the host."""
-        return self._split_bytes(self.L.hpn_bam_sort_stored_dev, "hpn_bam_sort_stored_dev")
+        return self._dev_span_bytes("hpn_bam_sort_stored_dev")
 
     # ---- samtools rmdup: duplicates of a coordinate-sorted BAM removed (hpn_bam_rmdup_*) ----
     def bam_rmdup_begin(self, n_ref, ids=(), lib_of_id=(), n_libs=1):
@@ -912,24 +915,19 @@ class Context:
 
     def bam_rmdup_blocks(self, n):
         """The n closed blocks of the last bam_rmdup_emit -> list of SplitBlock (off, len, crc, tid)."""
-        out = (_lib.SplitBlock * max(int(n), 1))()
-        got = C.c_uint64(0)
-        self._ck(self.L.hpn_bam_rmdup_blocks(self.h, 0, out, int(n), C.byref(got)), "hpn_bam_rmdup_blocks")
-        return out[:got.value]
+        return self._last_blocks("hpn_bam_rmdup_blocks", n)
 
     def bam_rmdup_payload(self):
         """The payload buffer of the last bam_rmdup_emit up to the end of its last closed block, copied to the host."""
-        return self._split_bytes(self.L.hpn_bam_rmdup_payload_dev, "hpn_bam_rmdup_payload_dev")
+        return self._dev_span_bytes("hpn_bam_rmdup_payload_dev")
 
     def bam_rmdup_payload_dev(self):
         """-> (device address, bytes) of the same, for callers that look at the buffer where it lies."""
-        p, n = C.c_void_p(0), C.c_uint64(0)
-        self._ck(self.L.hpn_bam_rmdup_payload_dev(self.h, C.byref(p), C.byref(n)), "hpn_bam_rmdup_payload_dev")
-        return p.value or 0, n.value
+        return self._dev_span("hpn_bam_rmdup_payload_dev")
 
     def bam_rmdup_stored(self):
         """The closed blocks of the last bam_rmdup_emit framed as stored BGZF blocks (level 0), copied to the host."""
-        return self._split_bytes(self.L.hpn_bam_rmdup_stored_dev, "hpn_bam_rmdup_stored_dev")
+        return self._dev_span_bytes("hpn_bam_rmdup_stored_dev")
 
     # ---- collectives / synthetic -----------------------------------------
     def comm_init(self, rank, n_ranks, unique_id: bytes):

@@ -11,7 +11,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "hpn_ctx.hpp"
+#include "hpn_bamrec.hpp"
 
 namespace hpn {
 // kernels/bam_bai.hip
@@ -46,9 +46,7 @@ struct hpn_bai_state : FamilyState {
     uint64_t records = 0, n_no_coor = 0, first_voffset = 0, end_voffset = 0;
     std::vector<uint64_t> h_wbase;
     std::vector<Head> h_heads;             // every run head since _begin, in file order
-    int64_t bad_record = -1;
-    int32_t bad_tid = 0, bad_pos = 0;
-    uint32_t reason = 0;
+    BadRecord bad;
     std::vector<hpn_bai_target> targets;
     std::vector<hpn_bai_chunk> chunks;
     std::vector<uint64_t> windows;
@@ -90,7 +88,7 @@ int hpn_bam_bai_begin(hpn_ctx *c, int32_t n_ref, const int32_t *target_len, uint
     u->open = true, u->dead = false, u->ended = false, u->finished = false;
     u->n_ref = n_ref, u->turn = 0, u->records = 0, u->n_no_coor = 0, u->first_voffset = first_voffset, u->end_voffset = first_voffset;
     u->h_heads.clear();
-    u->bad_record = -1, u->bad_tid = 0, u->bad_pos = 0, u->reason = 0;
+    u->bad = BadRecord();
     u->targets.clear(), u->chunks.clear(), u->windows.clear();
     return HPN_OK;
 }
@@ -106,7 +104,7 @@ int hpn_bam_bai_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, const hpn_bgzf_blo
     memset(info, 0, sizeof *info);
     const uint64_t n = d_raw ? c->r_n : 0;
     info->n_records = n;
-    info->bad_record = u->bad_record, info->bad_tid = u->bad_tid, info->bad_pos = u->bad_pos, info->reason = u->reason;
+    bad_report(u->bad, info);
     if (last) u->ended = true, u->end_voffset = end_voffset;
     if (u->dead || !n) return HPN_OK;
     if (!d_blocks || !block_addr || !n_blocks || n_blocks > 0xfffffff0ull) return fail(c, HPN_E_ARG, "hpn_bam_bai_add_raw_dev: records without their block table");
@@ -128,27 +126,20 @@ int hpn_bam_bai_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, const hpn_bgzf_blo
     HPN_HIP(c, hipMemcpyAsync(h, u->info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HPN_HIP(c, hipStreamSynchronize(c->stream));       // (also: `init` and block_addr are the caller's)
     if (h[0] != ~0ull) {                               // the first record outside the domain: refID and pos for the report
-        const uint64_t ord = h[0] >> 4;
-        uint64_t off = 0;
-        int32_t f[2] = {0, 0};
-        HPN_HIP(c, hipMemcpyAsync(&off, (const uint64_t *)c->r_off.p + (ord - u->records), sizeof off, hipMemcpyDeviceToHost, c->stream));
-        HPN_HIP(c, hipStreamSynchronize(c->stream));
-        HPN_HIP(c, hipMemcpyAsync(f, d_raw + off + 4, sizeof f, hipMemcpyDeviceToHost, c->stream));
-        HPN_HIP(c, hipStreamSynchronize(c->stream));
+        if ((rc = bad_from_batch(c, d_raw, h[0] >> 4, u->records, (uint32_t)(h[0] & 15), u->bad)) != HPN_OK) return rc;
         u->dead = true;
-        u->bad_record = (int64_t)ord, u->bad_tid = f[0], u->bad_pos = f[1], u->reason = (uint32_t)(h[0] & 15);
         u->records += n;
-        info->bad_record = u->bad_record, info->bad_tid = u->bad_tid, info->bad_pos = u->bad_pos, info->reason = u->reason;
+        bad_report(u->bad, info);
         return HPN_OK;
     }
     const uint64_t nh = h[2];
     if (nh > n) return fail(c, HPN_E_HIP, "hpn_bam_bai: %llu run heads in %llu records", (unsigned long long)nh, (unsigned long long)n);
     if (u->h_heads.size() + nh > kMaxHeads) {          // the lists are made on the host: what they may take there is bounded
         u->dead = true;
-        u->bad_record = (int64_t)u->records, u->bad_tid = 0, u->bad_pos = 0, u->reason = 9;
+        u->bad = BadRecord{(int64_t)u->records, 0, 0, 9};
         u->records += n;
         std::vector<Head>().swap(u->h_heads);
-        info->bad_record = u->bad_record, info->bad_tid = 0, info->bad_pos = 0, info->reason = 9;
+        bad_report(u->bad, info);
         return HPN_OK;
     }
     if (nh) {
@@ -175,7 +166,7 @@ int hpn_bam_bai_finish(hpn_ctx *c, hpn_bai_result *res)
     HPN_HIP(c, hipSetDevice(c->device));
     memset(res, 0, sizeof *res);
     res->n_records = u->records, res->n_no_coor = u->n_no_coor, res->n_ref = (uint32_t)u->n_ref;
-    res->bad_record = u->bad_record, res->bad_tid = u->bad_tid, res->bad_pos = u->bad_pos, res->reason = u->reason;
+    bad_report(u->bad, res);
     u->targets.assign((size_t)u->n_ref, hpn_bai_target{});
     u->chunks.clear(), u->windows.clear();
     u->open = false, u->finished = true;

@@ -50,6 +50,7 @@ struct Scratch {
 
 // What a session family (hpn_fastq_uniq_*, ..., hpn_bam_split_*, hpn_bam_bai_*, hpn_bam_sort_*, hpn_bam_rmdup_*) keeps between its calls: the context owns one per family, made
 // on first use.  A family's state names its slot as `kSlot`; a new family adds its slot here and nothing else outside its file.
+// (What the BAM families share -- BadRecord, the record store, the slices -- they hold as values: hpn_bamrec.hpp.)
 struct FamilyState {
     virtual ~FamilyState() = default;
 };

@@ -1,11 +1,14 @@
 // hpn_cuts.hpp -- samtools' writer rule as one launch sequence, shared by the sessions that write BAM: hpn_split.hip (a target's
-// records as they lie in the input) and hpn_bamsort.hip (the sorted records, slice by slice).  Kernels: kernels/bam_split.hip.
+// records as they lie in the input) and, through hpn_bamrec.hpp's SliceOut, hpn_bamsort.hip and hpn_rmdup.hip (stored records in
+// the order the family decided, slice by slice).  Kernels: kernels/bam_split.hip.
 //
 // A caller describes its payload buffer as m items -- item 0 the bytes of the block the call before left open, items 1 .. m - 1
 // its records -- by Q[0 .. m] (where an item starts, Q[m] the end) and key[0 .. m - 1] (the item's target; items of a key outside
 // [0, n_ref) make no block).  cut_blocks() lists the blocks bam_write1 would close, carry_open() takes the last one back while
 // it may still grow, close_blocks() gives the others their CRC-32 and, for level 0, their stored image.
 #pragma once
+#include <string.h>
+
 #include <vector>
 
 #include "hpn_ctx.hpp"
@@ -115,6 +118,18 @@ inline int close_blocks(hpn_ctx *c, CutWork &w, const uint8_t *pay, std::vector<
     for (size_t k = 0; k < nc; ++k) list[k].crc = crcs[k];
     *payload_bytes = list.back().off + list.back().len;
     return level0 ? stored_image(c, w, pay, list, stored_bytes) : (int)HPN_OK;
+}
+
+// The listed blocks from `first` on into out[0 .. cap): what a family's _blocks call answers.
+inline int list_blocks(hpn_ctx *c, const std::vector<hpn_split_block> &list, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
+{
+    const uint64_t have = list.size();
+    if (first > have) return fail(c, HPN_E_ARG, "block %llu of %llu", (unsigned long long)first, (unsigned long long)have);
+    *n = have - first;
+    if (*n > cap) return HPN_E_CAPACITY;
+    if (*n && !out) return HPN_E_ARG;
+    if (*n) memcpy(out, list.data() + first, (size_t)*n * sizeof(hpn_split_block));
+    return HPN_OK;
 }
 
 }  // namespace hpn

@@ -1,7 +1,7 @@
 // hpn_rmdup.hip -- C ABI of samtools' rmdup of a coordinate-sorted BAM (bam_rmdup.c, pairs): hpn_bam_rmdup_begin / _add_raw_dev /
 // _finish / _counts / _order / _emit / _blocks / _payload_dev / _stored_dev.  Kernels: kernels/bam_rmdup.hip; the gather, the
 // sizes and the items of a slice: kernels/bam_sort.hip; the radix sort and the scan through hpn_sort_pairs_u64_bits and
-// hpn_excl_scan (device pointers); the cuts, the CRC-32 and the stored framing: hpn_cuts.hpp.
+// hpn_excl_scan (device pointers); the record store and the slices (gather, cuts, CRC-32, stored framing): hpn_bamrec.hpp.
 //
 // The session sees the batches hpn_bam_raw_index_dev has indexed, in file order.  Per batch: every record's fields, class, name
 // hash, quality sum and library into arrays by ordinal -- the left neighbour of a batch's first record is the entry the batch
@@ -12,41 +12,26 @@
 
 #include <vector>
 
-#include "hpn_cuts.hpp"
-#include "hpn_store.hpp"
+#include "hpn_bamrec.hpp"
 #include "kernels/bam_rmdup.hpp"
-
-namespace hpn {
-// kernels/bam_sort.hip
-hipError_t launch_bamsort_psize(const uint32_t *size, const uint32_t *order, uint64_t n, uint32_t *psize, hipStream_t st);
-hipError_t launch_bamsort_items(const u64 *out_off, uint64_t first, uint64_t cnt, uint32_t fill, uint32_t open_key, u64 *Q, uint32_t *key, hipStream_t st);
-hipError_t launch_bamsort_gather(const uint8_t *store, const u64 *soff, const uint32_t *size, const uint32_t *order, const u64 *out_off, uint64_t first,
-                                 uint64_t cnt, uint8_t *pay, int n_cu, hipStream_t st);
-}  // namespace hpn
 
 using namespace hpn;
 
 namespace {
-constexpr uint64_t kMaxRecords = (1ull << 31) - 1;
 constexpr uint32_t kMaxIds = 1u << 16;
 }  // namespace
 
 struct hpn_rmdup_work {   // what a new session must not inherit
-    Scratch store, tp, cls, isize, qsum, lib, size, hash, soff;                                  // by ordinal, grown batch by batch
+    BamStore st;
+    SliceOut out;
+    Scratch tp, cls, isize, qsum, lib, hash;                                                     // by ordinal, grown batch by batch
     Scratch rb, hf, rsc, hsc, rid, runstart, evkind, evrec, slot, drop, now, sl, cnow, cslot;    // _finish
-    Scratch hkey, hval, ekey, eval, order, psize, out_off;
-    Scratch id_bytes, id_off, id_lib, libs, unmatched, present, info, cut_info, Q, ikey, pay, keep;
-    CutWork cw;
-    bool open = false, dead = false, finished = false, ended = false;
+    Scratch hkey, hval, ekey, eval, order;
+    Scratch id_bytes, id_off, id_lib, libs, unmatched, present, info;
+    bool open = false, dead = false, finished = false;
     uint32_t n_ref = 0, n_ids = 0, n_libs = 0;
-    uint64_t records = 0, store_len = 0, n_out = 0, n_heads = 0, payload = 0, emitted = 0;
-    uint32_t fill = 0;
-    int64_t bad_record = -1;
-    int32_t bad_tid = 0, bad_pos = 0;
-    uint32_t reason = 0;
-    std::vector<hpn_split_block> list;   // the closed blocks of the last _emit
-    uint64_t payload_bytes = 0, stored_bytes = 0;
-    bool stored_made = false;
+    uint64_t n_out = 0, n_heads = 0;
+    BadRecord bad;
 };
 
 struct hpn_rmdup_state : FamilyState, hpn_rmdup_work {
@@ -66,8 +51,8 @@ hpn_rmdup_state *live(hpn_ctx *c, const char *who, bool want_finished)
 
 RmArrays arrays_of(hpn_rmdup_state *u)
 {
-    return RmArrays{(u64 *)u->tp.p, (uint32_t *)u->cls.p, (uint32_t *)u->isize.p, (uint32_t *)u->qsum.p, (uint32_t *)u->lib.p, (uint32_t *)u->size.p,
-                    (u64 *)u->hash.p, (u64 *)u->soff.p};
+    return RmArrays{(u64 *)u->tp.p, (uint32_t *)u->cls.p, (uint32_t *)u->isize.p, (uint32_t *)u->qsum.p, (uint32_t *)u->lib.p, (uint32_t *)u->st.size.p,
+                    (u64 *)u->hash.p, (u64 *)u->st.soff.p};
 }
 
 // the record the device names: its refID and pos for the caller's message
@@ -78,15 +63,8 @@ int note_bad(hpn_ctx *c, hpn_rmdup_state *u, u64 word)
     HPN_HIP(c, hipMemcpyAsync(&tp, (const u64 *)u->tp.p + ord, sizeof tp, hipMemcpyDeviceToHost, c->stream));
     HPN_HIP(c, hipStreamSynchronize(c->stream));
     u->dead = true;
-    u->bad_record = (int64_t)ord, u->bad_tid = (int32_t)(tp >> 32), u->bad_pos = (int32_t)(uint32_t)tp, u->reason = (uint32_t)(word & 15);
+    u->bad.record = (int64_t)ord, u->bad.tid = (int32_t)(tp >> 32), u->bad.pos = (int32_t)(uint32_t)tp, u->bad.reason = (uint32_t)(word & 15);
     return HPN_OK;
-}
-
-int bits_of(uint64_t v)
-{
-    int b = 0;
-    for (; v; v >>= 1) ++b;
-    return b;
 }
 
 }  // namespace
@@ -109,8 +87,8 @@ int hpn_bam_rmdup_begin(hpn_ctx *c, int32_t n_ref, uint32_t n_ids, const char *c
     static_cast<hpn_rmdup_work &>(*u) = hpn_rmdup_work();
     u->n_ref = (uint32_t)n_ref, u->n_ids = n_ids, u->n_libs = n_libs;
     int rc;
-    if ((rc = scratch_reserve(c, u->info, kRmWords * sizeof(u64))) != HPN_OK || (rc = scratch_reserve(c, u->cut_info, 64)) != HPN_OK ||
-        (rc = scratch_reserve(c, u->keep, kCutFull + 64)) != HPN_OK || (rc = scratch_reserve(c, u->id_bytes, bytes.size() + 64)) != HPN_OK ||
+    if ((rc = scratch_reserve(c, u->info, kRmWords * sizeof(u64))) != HPN_OK || (rc = sliceout_begin(c, u->out)) != HPN_OK ||
+        (rc = scratch_reserve(c, u->id_bytes, bytes.size() + 64)) != HPN_OK ||
         (rc = scratch_reserve(c, u->id_off, off.size() * 4)) != HPN_OK || (rc = scratch_reserve(c, u->id_lib, (lib.size() + 1) * 4)) != HPN_OK ||
         (rc = scratch_reserve(c, u->libs, (size_t)n_libs * 3 * sizeof(u64))) != HPN_OK ||
         (rc = scratch_reserve(c, u->unmatched, ((size_t)n_ref + 1) * sizeof(u64))) != HPN_OK ||
@@ -141,44 +119,36 @@ int hpn_bam_rmdup_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, hpn_rmdup_info *
     HPN_HIP(c, hipSetDevice(c->device));
     memset(info, 0, sizeof *info);
     const uint64_t n = d_raw ? c->r_n : 0;
-    auto report = [&]() {
-        info->n_records = n, info->store_bytes = u->store_len;
-        info->bad_record = u->bad_record, info->bad_tid = u->bad_tid, info->bad_pos = u->bad_pos, info->reason = u->reason;
-    };
+    BamStore &st = u->st;
+    auto report = [&]() { info->n_records = n, info->store_bytes = st.len, bad_report(u->bad, info); };
     report();
     if (u->dead || !n) return HPN_OK;
-    if (u->records + n > kMaxRecords) {                // the first record the session cannot take
+    if (st.records + n > kMaxRecords) {                // the first record the session cannot take
         u->dead = true;
-        u->bad_record = (int64_t)kMaxRecords, u->reason = kRsRecords;
-        u->records += n;
+        u->bad.record = (int64_t)kMaxRecords, u->bad.reason = kRsRecords;
+        st.records += n;
         report();
         return HPN_OK;
     }
     int rc;
-    const uint64_t have = u->records, all = have + n;
+    const uint64_t have = st.records, all = have + n;
     if ((rc = grow_keep(c, u->tp, all * 8, have * 8)) != HPN_OK || (rc = grow_keep(c, u->cls, all * 4, have * 4)) != HPN_OK ||
         (rc = grow_keep(c, u->isize, all * 4, have * 4)) != HPN_OK || (rc = grow_keep(c, u->qsum, all * 4, have * 4)) != HPN_OK ||
-        (rc = grow_keep(c, u->lib, all * 4, have * 4)) != HPN_OK || (rc = grow_keep(c, u->size, all * 4, have * 4)) != HPN_OK ||
-        (rc = grow_keep(c, u->hash, all * 8, have * 8)) != HPN_OK || (rc = grow_keep(c, u->soff, all * 8, have * 8)) != HPN_OK)
+        (rc = grow_keep(c, u->lib, all * 4, have * 4)) != HPN_OK || (rc = grow_keep(c, u->hash, all * 8, have * 8)) != HPN_OK ||
+        (rc = bamstore_grow(c, st, n)) != HPN_OK)
         return rc;
     const RmIds ids = {(const uint8_t *)u->id_bytes.p, (const uint32_t *)u->id_off.p, (const uint32_t *)u->id_lib.p, u->n_ids};
-    HPN_HIP(c, launch_rmdup_classify(d_raw, (const uint64_t *)c->r_off.p, n, have, u->store_len, u->n_ref, arrays_of(u), ids, (u64 *)u->info.p, c->stream));
+    HPN_HIP(c, launch_rmdup_classify(d_raw, (const uint64_t *)c->r_off.p, n, have, st.len, u->n_ref, arrays_of(u), ids, (u64 *)u->info.p, c->stream));
     u64 h[3];
     HPN_HIP(c, hipMemcpyAsync(h, u->info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HPN_HIP(c, hipStreamSynchronize(c->stream));
-    u->records = all;
     if (h[kRmBad] != ~0ull) {
+        st.records = all;
         if ((rc = note_bad(c, u, h[kRmBad])) != HPN_OK) return rc;
         report();
         return HPN_OK;
     }
-    if (h[kRmEnd] < h[kRmFirst]) return fail(c, HPN_E_HIP, "hpn_bam_rmdup: the batch's records end at %llu, in front of their start %llu",
-                                             (unsigned long long)h[kRmEnd], (unsigned long long)h[kRmFirst]);
-    const uint64_t rec_bytes = h[kRmEnd] - h[kRmFirst];
-    if ((rc = grow_keep(c, u->store, u->store_len + rec_bytes + 64, u->store_len)) != HPN_OK) return rc;
-    HPN_HIP(c, hipMemcpyAsync((uint8_t *)u->store.p + u->store_len, d_raw + h[kRmFirst], rec_bytes, hipMemcpyDeviceToDevice, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));       // (the caller's d_raw is free to go)
-    u->store_len += rec_bytes;
+    if ((rc = bamstore_append(c, st, d_raw, h[kRmFirst], h[kRmEnd], n, "hpn_bam_rmdup")) != HPN_OK) return rc;
     report();
     return HPN_OK;
 }
@@ -193,21 +163,21 @@ int hpn_bam_rmdup_finish(hpn_ctx *c, hpn_rmdup_result *res)
     memset(res, 0, sizeof *res);
     u->finished = true;
     auto report = [&]() {
-        res->n_records = u->records, res->n_out = u->n_out, res->payload_bytes = u->payload, res->n_heads = u->n_heads;
-        res->bad_record = u->bad_record, res->bad_tid = u->bad_tid, res->bad_pos = u->bad_pos, res->reason = u->reason;
+        res->n_records = u->st.records, res->n_out = u->n_out, res->payload_bytes = u->out.payload, res->n_heads = u->n_heads;
+        bad_report(u->bad, res);
         res->n_libs = u->n_libs, res->n_ref = u->n_ref;
     };
     report();
     if (u->dead) return HPN_OK;
-    const uint64_t n = u->records;
+    const uint64_t n = u->st.records;
     int rc;
-    Scratch *per_record[] = {&u->rb, &u->hf, &u->rid, &u->evkind, &u->evrec, &u->slot, &u->drop, &u->now, &u->sl, &u->hval, &u->eval, &u->order, &u->psize};
+    Scratch *per_record[] = {&u->rb, &u->hf, &u->rid, &u->evkind, &u->evrec, &u->slot, &u->drop, &u->now, &u->sl, &u->hval, &u->eval, &u->order};
     for (Scratch *s : per_record)
         if ((rc = need(c, *s, n * 4)) != HPN_OK) return rc;
     Scratch *scanned[] = {&u->rsc, &u->hsc, &u->cnow, &u->cslot, &u->runstart};
     for (Scratch *s : scanned)
         if ((rc = need(c, *s, (n + 2) * 4)) != HPN_OK) return rc;
-    if ((rc = need(c, u->hkey, n * 8)) != HPN_OK || (rc = need(c, u->ekey, n * 8)) != HPN_OK || (rc = need(c, u->out_off, (n + 1) * 8)) != HPN_OK) return rc;
+    if ((rc = need(c, u->hkey, n * 8)) != HPN_OK || (rc = need(c, u->ekey, n * 8)) != HPN_OK || (rc = sliceout_reserve(c, u->out, n)) != HPN_OK) return rc;
     const RmArrays A = arrays_of(u);
     const RmWork W = {(uint32_t *)u->rb.p,     (uint32_t *)u->hf.p,    (uint32_t *)u->rsc.p,  (uint32_t *)u->hsc.p,  (uint32_t *)u->rid.p,
                       (uint32_t *)u->runstart.p, (uint32_t *)u->evkind.p, (uint32_t *)u->evrec.p, (uint32_t *)u->slot.p, (uint32_t *)u->drop.p,
@@ -238,7 +208,7 @@ int hpn_bam_rmdup_finish(hpn_ctx *c, hpn_rmdup_result *res)
         HPN_HIP(c, launch_rmdup_evkey(A, W, n, ekey, eval, c->stream));
         HPN_HIP(c, hipStreamSynchronize(c->stream));
         if (n > 1 && (rc = hpn_sort_pairs_u64_bits(c, (uint64_t *)ekey, eval, n, 0, 64)) != HPN_OK) return rc;
-        HPN_HIP(c, launch_rmdup_names((const uint8_t *)u->store.p, A, W, n, ekey, eval, (u64 *)u->unmatched.p, (u64 *)u->info.p, c->stream));
+        HPN_HIP(c, launch_rmdup_names((const uint8_t *)u->st.store.p, A, W, n, ekey, eval, (u64 *)u->unmatched.p, (u64 *)u->info.p, c->stream));
         u64 bad = ~0ull;
         HPN_HIP(c, hipMemcpyAsync(&bad, u->info.p, sizeof bad, hipMemcpyDeviceToHost, c->stream));
         HPN_HIP(c, hipStreamSynchronize(c->stream));
@@ -259,15 +229,8 @@ int hpn_bam_rmdup_finish(hpn_ctx *c, hpn_rmdup_result *res)
         if (u->n_out > n) return fail(c, HPN_E_HIP, "hpn_bam_rmdup: %llu records out of %llu", (unsigned long long)u->n_out, (unsigned long long)n);
         HPN_HIP(c, hipMemsetAsync(order, 0, n * 4, c->stream));          // (every entry is written below; an ordinal in any case)
         HPN_HIP(c, launch_rmdup_place(W, n, u->n_out, order, c->stream));
-        HPN_HIP(c, launch_bamsort_psize((const uint32_t *)u->size.p, order, u->n_out, (uint32_t *)u->psize.p, c->stream));
-        HPN_HIP(c, hipStreamSynchronize(c->stream));
     }
-    if ((rc = hpn_excl_scan(c, u->n_out ? u->psize.p : nullptr, 32, u->out_off.p, 64, u->n_out)) != HPN_OK) return rc;
-    HPN_HIP(c, hipMemcpyAsync(&u->payload, (const u64 *)u->out_off.p + u->n_out, 8, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (u->payload > u->store_len)
-        return fail(c, HPN_E_HIP, "hpn_bam_rmdup: the surviving records take %llu bytes, the store holds %llu", (unsigned long long)u->payload,
-                    (unsigned long long)u->store_len);
+    if ((rc = sliceout_offsets(c, u->out, u->st, order, u->n_out, false, "hpn_bam_rmdup")) != HPN_OK) return rc;
     report();
     return HPN_OK;
 }
@@ -310,53 +273,7 @@ int hpn_bam_rmdup_emit(hpn_ctx *c, uint64_t first_record, uint64_t max_records, 
     if (!c || !info) return HPN_E_ARG;
     hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_emit", true);
     if (!u) return HPN_E_STATE;
-    if (u->ended) return fail(c, HPN_E_STATE, "hpn_bam_rmdup_emit behind the call that ended the file");
-    if (first_record != u->emitted)
-        return fail(c, HPN_E_ARG, "hpn_bam_rmdup_emit: slice from record %llu, the next one is %llu (the open block is carried from slice to slice)",
-                    (unsigned long long)first_record, (unsigned long long)u->emitted);
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    info->bad_record = -1, info->tid_first = 0, info->tid_last = -1;
-    u->list.clear(), u->payload_bytes = 0, u->stored_bytes = 0, u->stored_made = false;
-    const uint64_t left = u->n_out - first_record, cnt = max_records < left ? max_records : left;
-    if (cnt > 0xfffffff0ull) return fail(c, HPN_E_ARG, "more than 2^32 records in one slice");
-    if (last && cnt != left) return fail(c, HPN_E_ARG, "hpn_bam_rmdup_emit: last = 1 with %llu records behind the slice", (unsigned long long)(left - cnt));
-    info->n_records = cnt;
-    const uint64_t m = cnt + 1;
-    int rc;
-    u64 span[2] = {0, 0};      // the slice's bytes in the output's payload
-    if (cnt) {
-        HPN_HIP(c, hipMemcpyAsync(&span[0], (const u64 *)u->out_off.p + first_record, 8, hipMemcpyDeviceToHost, c->stream));
-        HPN_HIP(c, hipMemcpyAsync(&span[1], (const u64 *)u->out_off.p + first_record + cnt, 8, hipMemcpyDeviceToHost, c->stream));
-        HPN_HIP(c, hipStreamSynchronize(c->stream));
-        if (span[1] < span[0] || span[1] > u->payload) return fail(c, HPN_E_HIP, "hpn_bam_rmdup: the slice's offsets are out of order");
-    }
-    const uint64_t rec_bytes = span[1] - span[0], total = u->fill + rec_bytes;
-    if ((rc = scratch_reserve(c, u->Q, (m + 1) * sizeof(u64))) != HPN_OK || (rc = scratch_reserve(c, u->ikey, (m + 1) * sizeof(uint32_t))) != HPN_OK ||
-        (rc = cut_reserve(c, u->cw, m)) != HPN_OK || (rc = scratch_reserve(c, u->pay, total + 64)) != HPN_OK)
-        return rc;
-    const u64 init[4] = {~0ull, 0, 0, 0};
-    HPN_HIP(c, hipMemcpyAsync(u->cut_info.p, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-    if (u->fill) HPN_HIP(c, hipMemcpyAsync(u->pay.p, u->keep.p, u->fill, hipMemcpyDeviceToDevice, c->stream));
-    HPN_HIP(c, launch_bamsort_items((const u64 *)u->out_off.p, first_record, cnt, u->fill, u->fill ? 0u : kCutNoKey, (u64 *)u->Q.p, (uint32_t *)u->ikey.p,
-                                    c->stream));
-    HPN_HIP(c, hipEventRecord(c->ev_beg[kFamTrim], c->stream));
-    HPN_HIP(c, launch_bamsort_gather((const uint8_t *)u->store.p, (const u64 *)u->soff.p, (const uint32_t *)u->size.p, (const uint32_t *)u->order.p,
-                                     (const u64 *)u->out_off.p, first_record, cnt, (uint8_t *)u->pay.p + u->fill, c->n_cu, c->stream));
-    HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
-    c->ev_valid[kFamTrim] = true;
-    HPN_HIP(c, hipStreamSynchronize(c->stream));       // (`init` is this call's)
-    if ((rc = cut_blocks(c, u->cw, (const u64 *)u->Q.p, (const uint32_t *)u->ikey.p, m, 1, (u64 *)u->cut_info.p, total, u->list, "hpn_bam_rmdup")) != HPN_OK)
-        return rc;
-    int32_t open_tid = -1;
-    if ((rc = carry_open(c, u->keep, (const uint8_t *)u->pay.p, u->list, total, last != 0, &u->fill, &open_tid)) != HPN_OK) return rc;
-    if (last) u->ended = true;
-    if ((rc = close_blocks(c, u->cw, (const uint8_t *)u->pay.p, u->list, false, &u->payload_bytes, &u->stored_bytes)) != HPN_OK) return rc;
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    u->emitted += cnt;
-    info->n_blocks = u->list.size(), info->payload_bytes = u->payload_bytes, info->open_bytes = u->fill;
-    if (!u->list.empty()) info->tid_first = info->tid_last = 0;
-    return HPN_OK;
+    return sliceout_emit(c, u->out, u->st, (const uint32_t *)u->order.p, u->n_out, first_record, max_records, last, info, "hpn_bam_rmdup");
 }
 
 int hpn_bam_rmdup_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
@@ -364,13 +281,7 @@ int hpn_bam_rmdup_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint6
     if (!c || !n) return HPN_E_ARG;
     hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_blocks", true);
     if (!u) return HPN_E_STATE;
-    const uint64_t have = u->list.size();
-    if (first > have) return fail(c, HPN_E_ARG, "block %llu of %llu", (unsigned long long)first, (unsigned long long)have);
-    *n = have - first;
-    if (*n > cap) return HPN_E_CAPACITY;
-    if (*n && !out) return HPN_E_ARG;
-    if (*n) memcpy(out, u->list.data() + first, (size_t)*n * sizeof(hpn_split_block));
-    return HPN_OK;
+    return list_blocks(c, u->out.list, first, out, cap, n);
 }
 
 int hpn_bam_rmdup_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n_bytes)
@@ -378,24 +289,15 @@ int hpn_bam_rmdup_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n
     if (!c || !d_payload || !n_bytes) return HPN_E_ARG;
     hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_payload_dev", true);
     if (!u) return HPN_E_STATE;
-    *d_payload = (const uint8_t *)u->pay.p, *n_bytes = u->payload_bytes;
-    return HPN_OK;
+    return sliceout_payload(u->out, d_payload, n_bytes);
 }
 
-// (made when it is asked for: only a level-0 writer wants it)
 int hpn_bam_rmdup_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_bytes)
 {
     if (!c || !d_image || !n_bytes) return HPN_E_ARG;
     hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_stored_dev", true);
     if (!u) return HPN_E_STATE;
-    HPN_HIP(c, hipSetDevice(c->device));
-    if (!u->stored_made) {
-        const int rc = stored_image(c, u->cw, (const uint8_t *)u->pay.p, u->list, &u->stored_bytes);
-        if (rc != HPN_OK) return rc;
-        u->stored_made = true;
-    }
-    *d_image = (const uint8_t *)u->cw.img.p, *n_bytes = u->stored_bytes;
-    return HPN_OK;
+    return sliceout_stored(c, u->out, d_image, n_bytes);
 }
 
 }  // extern "C"

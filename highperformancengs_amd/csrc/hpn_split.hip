@@ -8,7 +8,7 @@
 
 #include <vector>
 
-#include "hpn_cuts.hpp"
+#include "hpn_bamrec.hpp"
 
 namespace hpn {
 // kernels/bam_split.hip (the cuts, the block list and the stored framing: hpn_cuts.hpp)
@@ -34,9 +34,7 @@ struct hpn_split_state : FamilyState {
     uint64_t records = 0, n_blocks = 0;
     uint32_t fill = 0;               // bytes of the open block (in `keep`)
     int32_t open_tid = -1;
-    int64_t bad_record = -1;
-    int32_t bad_tid = 0, bad_pos = 0;
-    uint32_t reason = 0;
+    BadRecord bad;
     std::vector<hpn_split_block> list;   // the closed blocks of the last call
     uint64_t payload_bytes = 0, stored_bytes = 0;
 };
@@ -57,14 +55,14 @@ int hpn_bam_split_begin(hpn_ctx *c, int32_t n_ref, int level0)
     u->open = true, u->dead = false, u->ended = false;
     u->n_ref = n_ref, u->level0 = level0 != 0;
     u->turn = 0, u->records = 0, u->n_blocks = 0, u->fill = 0, u->open_tid = -1;
-    u->bad_record = -1, u->bad_tid = 0, u->bad_pos = 0, u->reason = 0;
+    u->bad = BadRecord();
     u->list.clear(), u->payload_bytes = 0, u->stored_bytes = 0;
     return HPN_OK;
 }
 
 static void split_report(const hpn_split_state *u, hpn_split_info *info)
 {
-    info->bad_record = u->bad_record, info->bad_tid = u->bad_tid, info->bad_pos = u->bad_pos, info->reason = u->reason;
+    bad_report(u->bad, info);
     info->tid_first = 0, info->tid_last = -1;
 }
 
@@ -98,15 +96,8 @@ int hpn_bam_split_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, int last, hpn_sp
     HPN_HIP(c, hipStreamSynchronize(c->stream));       // (also: `init` is the caller's stack)
     u->turn ^= 1;
     if (h[0] != ~0ull) {                               // the first record outside the domain: refID and pos for the message
-        const uint64_t ord = h[0] >> 3;
-        uint64_t off = 0;
-        int32_t f[2] = {0, 0};
-        HPN_HIP(c, hipMemcpyAsync(&off, (const uint64_t *)c->r_off.p + (ord - u->records), sizeof off, hipMemcpyDeviceToHost, c->stream));
-        HPN_HIP(c, hipStreamSynchronize(c->stream));
-        HPN_HIP(c, hipMemcpyAsync(f, d_raw + off + 4, sizeof f, hipMemcpyDeviceToHost, c->stream));
-        HPN_HIP(c, hipStreamSynchronize(c->stream));
+        if ((rc = bad_from_batch(c, d_raw, h[0] >> 3, u->records, (uint32_t)(h[0] & 7), u->bad)) != HPN_OK) return rc;
         u->dead = true;
-        u->bad_record = (int64_t)ord, u->bad_tid = f[0], u->bad_pos = f[1], u->reason = (uint32_t)(h[0] & 7);
         u->records += n;
         split_report(u, info);
         return HPN_OK;
@@ -151,13 +142,7 @@ int hpn_bam_split_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint6
     if (!c || !n) return HPN_E_ARG;
     hpn_split_state *u = state<hpn_split_state>(c);
     if (!u || !u->open) return fail(c, HPN_E_STATE, "hpn_bam_split_blocks before hpn_bam_split_begin");
-    const uint64_t have = u->list.size();
-    if (first > have) return fail(c, HPN_E_ARG, "block %llu of %llu", (unsigned long long)first, (unsigned long long)have);
-    *n = have - first;
-    if (*n > cap) return HPN_E_CAPACITY;
-    if (*n && !out) return HPN_E_ARG;
-    if (*n) memcpy(out, u->list.data() + first, (size_t)*n * sizeof(hpn_split_block));
-    return HPN_OK;
+    return list_blocks(c, u->list, first, out, cap, n);
 }
 
 int hpn_bam_split_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n_bytes)
@@ -188,7 +173,7 @@ int hpn_bam_split_finish(hpn_ctx *c, hpn_split_result *res, uint64_t *counts)
     HPN_HIP(c, hipSetDevice(c->device));
     memset(res, 0, sizeof *res);
     res->n_records = u->records, res->n_blocks = u->n_blocks, res->n_ref = (uint32_t)u->n_ref;
-    res->bad_record = u->bad_record, res->bad_tid = u->bad_tid, res->bad_pos = u->bad_pos, res->reason = u->reason;
+    bad_report(u->bad, res);
     if (counts && u->n_ref) {
         // (per batch the counts moved by ordinals INSIDE the batch: every batch adds its own records, the sums are the file's)
         HPN_HIP(c, hipMemcpyAsync(counts, u->counts.p, (size_t)u->n_ref * sizeof(u64), hipMemcpyDeviceToHost, c->stream));

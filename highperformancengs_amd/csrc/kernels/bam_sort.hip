@@ -12,6 +12,7 @@
 //   k_sort_psize    psize[j] = size[order[j]]
 //   k_sort_items    a slice of the sorted records as the items of the cut kernels (kernels/bam_split.hip): Q and key
 //   k_sort_gather   16 lanes a record: record order[j] from the store to its place in the slice's payload
+#include "bam_sort.hpp"
 #include "common.hpp"
 
 namespace hpn {
@@ -22,13 +23,6 @@ constexpr unsigned kBsGatherBlocksPerCu = 0;    // (the test-hooks build: 16 wor
 #else
 constexpr unsigned kBsGatherBlocksPerCu = 8;
 #endif
-
-// info (u64 words, kept on the device from _begin to _finish):
-//   [0] lowest (ordinal << 3 | reason), ~0 none      [1] stream offset of the batch's first record   [2] ... behind its last
-//   [3] smallest high word below 2^31 (~0 none)       [4] largest such + 1 (0 none)
-//   [5] smallest high word from 2^31 up (~0 none)     [6] largest such - 0x7fffffff (0 none)
-//   [7] sum of 72 + kroundup32(block_size - 32)       [8] largest remapped key (k_sort_rank)
-enum { kBsBad = 0, kBsFirst, kBsEnd, kBsLoMin, kBsLoMax, kBsHiMin, kBsHiMax, kBsMem, kBsMaxKey, kBsWords = 16 };
 
 __device__ __forceinline__ u64 wave_min64(u64 v)
 {

@@ -12,9 +12,7 @@
 // HPN_BAM_GPU=0 selects that route from the start.  HPN_TIMING=1 says which route ran.
 #include <sys/stat.h>
 
-#include "../host/bai_build.hpp"
-#include "../host/bam_gpu.hpp"
-#include "../host/report.hpp"
+#include "../host/bam_tool.hpp"
 
 using namespace hpn;
 
@@ -25,13 +23,10 @@ static int index_device(hpn_ctx *ctx, const char *path, bai::Index &ix, std::str
     if (stat(path, &sb) != 0) return 1;
     const uint64_t file_size = (uint64_t)sb.st_size;
     {   // bam_header_read looks for the EOF marker first and only remarks on its absence
-        static const uint8_t marker[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        uint8_t tail[28];
         FILE *f = fopen(path, "rb");
         if (!f) return 1;
-        const bool have = file_size >= 28 && fseeko(f, -28, SEEK_END) == 0 && fread(tail, 1, 28, f) == 28 && memcmp(tail, marker, 28) == 0;
+        if (!bai::has_eof_marker(f)) said += "[bam_header_read] EOF marker is absent. The input is probably truncated.\n";
         fclose(f);
-        if (!have) said += "[bam_header_read] EOF marker is absent. The input is probably truncated.\n";
     }
     BgzfGpuStream bam;
     BamHeader hdr;
@@ -49,21 +44,8 @@ static int index_device(hpn_ctx *ctx, const char *path, bai::Index &ix, std::str
     if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_bai_begin");
     double t_ingest = 0, t_index = 0, t0;
     uint64_t n_batches = 0, n_runs = 0;
-    bool empty_seen = false;
     std::vector<uint64_t> addr;
-    for (;;) {
-        hpn_raw_info info;
-        t0 = wall_s();
-        const int r = bam.next(&info);
-        t_ingest += wall_s() - t0;
-        if (r < 0) return 1;
-        if (r == 0) break;
-        const BgzfDevice &dev = bam.device();
-        if (!dev.n_blocks()) continue;
-        // a block of no bytes ends the stream for samtools' reader: only the file's last block may be one
-        if (empty_seen || dev.empty_blocks() > 1 || (dev.empty_blocks() == 1 && !dev.last_block_empty())) return 1;
-        empty_seen = dev.empty_blocks() != 0;
-        if (!info.n_records) continue;
+    const bool fed = each_batch(bam, &t_ingest, [&](const BgzfDevice &dev) {
         addr.resize(dev.n_blocks() + 1);
         for (size_t k = 0; k <= dev.n_blocks(); ++k) addr[k] = bam.batch_file_offset() + dev.block_rel()[k];
         hpn_bai_info bi;
@@ -75,9 +57,11 @@ static int index_device(hpn_ctx *ctx, const char *path, bai::Index &ix, std::str
             if (timing)
                 fprintf(stderr, "[hpn] bam_index: record %lld (refID %d, pos %d) is outside the device's domain (reason %u)\n", (long long)bi.bad_record, bi.bad_tid,
                         bi.bad_pos, bi.reason);
-            return 1;
+            return false;
         }
-    }
+        return true;
+    });
+    if (!fed) return 1;
     if (!bam.plain_headers()) return 1;
     hpn_bai_info bi;
     if ((rc = hpn_bam_bai_add_raw_dev(ctx, nullptr, nullptr, 0, nullptr, 1, file_size << 16, &bi)) != HPN_OK) die_hpn(ctx, rc, "hpn_bam_bai_add_raw_dev");

@@ -14,32 +14,17 @@
 
 #include <algorithm>
 
-#include "../host/bam_gpu.hpp"
 #include "../host/bam_rmdup_host.hpp"
-#include "../host/report.hpp"
+#include "../host/bam_tool.hpp"
 
 using namespace hpn;
-
-#ifdef HPN_TEST_HOOKS
-static const uint64_t kSliceRecords = 1000;        // (the test-hooks build: the open block is carried over many slices)
-#else
-static const uint64_t kSliceRecords = 1u << 22;    // ~1 GB of payload per slice at 250 bytes a record
-#endif
 
 // 0 the output is written, 1 not for the device (the host route starts over; nothing has been said, no output is left)
 static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
 {
     std::string said;
     bamsort::Header hdr;
-    {   // the header on the host: its blocks are the writer's first, its @RG lines the device's table
-        FILE *f = fopen(o.in, "rb");
-        if (!f) return 1;
-        if (!bai::has_eof_marker(f)) said += "[bam_header_read] EOF marker is absent. The input is probably truncated.\n";
-        bai::BgzfSeq z(f);
-        const int hr = bamsort::read_header(z, hdr);
-        fclose(f);
-        if (hr != 0) return 1;
-    }
+    if (!open_bam_header(o.in, hdr, said)) return 1;   // on the host: its blocks are the writer's first, its @RG lines the device's table
     std::map<std::string, std::string> tbl;
     if (!rmdup::id_table(hdr.text, tbl)) return 1;
     std::vector<std::string> lib_name(1, "\t");       // library 0: no RG, an unknown ID, no LB
@@ -59,34 +44,23 @@ static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
     int rc = hpn_bam_rmdup_begin(ctx, (int32_t)hdr.name.size(), (uint32_t)ids.size(), ids.data(), lib_of_id.data(), (uint32_t)lib_name.size());
     if (rc == HPN_E_ARG || rc == HPN_E_NOMEM) return 1;       // (more IDs than the table takes)
     if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_begin");
-    double t_ingest = 0, t_store = 0, t_decide = 0, t_emit = 0, t_copy = 0, t_hand = 0, t0;
-    uint64_t n_batches = 0, n_blocks = 0;
-    bool empty_seen = false;
+    double t_ingest = 0, t_store = 0, t_decide = 0, t0;
+    uint64_t n_batches = 0;
     auto outside = [&](long long rec, int tid, int pos, unsigned reason) {
         if (timing) fprintf(stderr, "[hpn] bam_rmdup: record %lld (refID %d, pos %d) is outside the device's domain (reason %u)\n", rec, tid, pos, reason);
         return 1;
     };
-    for (;;) {
-        hpn_raw_info info;
-        t0 = wall_s();
-        const int r = bam.next(&info);
-        t_ingest += wall_s() - t0;
-        if (r < 0) return 1;
-        if (r == 0) break;
-        const BgzfDevice &dev = bam.device();
-        if (!dev.n_blocks()) continue;
-        // a block of no bytes ends the stream for samtools' reader: only the file's last block may be one
-        if (empty_seen || dev.empty_blocks() > 1 || (dev.empty_blocks() == 1 && !dev.last_block_empty())) return 1;
-        empty_seen = dev.empty_blocks() != 0;
-        if (!info.n_records) continue;
+    const bool fed = each_batch(bam, &t_ingest, [&](const BgzfDevice &) {
         hpn_rmdup_info ri;
         t0 = wall_s();
         rc = hpn_bam_rmdup_add_raw_dev(ctx, bam.d_raw(), &ri);
-        if (rc == HPN_E_NOMEM) return 1;                   // the working set does not fit the device
+        if (rc == HPN_E_NOMEM) return false;               // the working set does not fit the device
         if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_add_raw_dev");
         t_store += wall_s() - t0, ++n_batches;
-        if (ri.bad_record >= 0) return outside((long long)ri.bad_record, ri.bad_tid, ri.bad_pos, ri.reason);
-    }
+        if (ri.bad_record >= 0) return outside((long long)ri.bad_record, ri.bad_tid, ri.bad_pos, ri.reason) == 0;
+        return true;
+    });
+    if (!fed) return 1;
     hpn_rmdup_result res;
     t0 = wall_s();
     rc = hpn_bam_rmdup_finish(ctx, &res);
@@ -101,46 +75,20 @@ static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
     std::vector<uint8_t> head_blocks;
     if (!bgzf_plain_blocks(head.data(), head.size(), -1, head_blocks)) return 1;
     BgzfWriter writer(-1);
-    bool created = false;
-    auto give_up = [&]() {      // the output so far goes; the host route makes it again
-        if (created) {
-            writer.abandon();
-            unlink(o.out);
+    SliceRun run;
+    const SliceCalls calls = {"hpn_bam_rmdup", hpn_bam_rmdup_emit, hpn_bam_rmdup_blocks, hpn_bam_rmdup_payload_dev, hpn_bam_rmdup_stored_dev};
+    // (the output is a file: whenever the device's memory runs out it can go, and the host route makes it again)
+    const int ws = write_slices(ctx, calls, res.n_out, -1, writer, false, [&]() {
+        if (!writer.begin(o.out, head_blocks)) {
+            fputs(said.c_str(), stderr);
+            fputs("[bam_rmdup] fail to read/write input files\n", stderr);
+            leave(1);
         }
+        return true;
+    }, run);
+    if (ws == kSlicesNoMem) {   // the output so far goes; the host route makes it again
+        if (run.created) writer.abandon(), unlink(o.out);
         return 1;
-    };
-    std::vector<hpn_split_block> blocks;
-    std::vector<uint8_t> bytes;
-    for (uint64_t first = 0;;) {
-        const uint64_t cnt = res.n_out - first < kSliceRecords ? res.n_out - first : kSliceRecords;
-        const bool last = first + cnt == res.n_out;
-        hpn_split_info si;
-        t0 = wall_s();
-        rc = hpn_bam_rmdup_emit(ctx, first, cnt, last ? 1 : 0, &si);
-        if (rc == HPN_E_NOMEM) return give_up();
-        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_emit");
-        t_emit += wall_s() - t0, t0 = wall_s();
-        uint64_t nb = 0, n = 0;
-        const uint8_t *d = nullptr;
-        blocks.resize(si.n_blocks);
-        if ((rc = hpn_bam_rmdup_blocks(ctx, 0, blocks.data(), blocks.size(), &nb)) != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_blocks");
-        if ((rc = hpn_bam_rmdup_payload_dev(ctx, &d, &n)) != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_payload_dev");
-        bytes.resize(n);
-        if (n && ((rc = hpn_memcpy_d2h(ctx, bytes.data(), d, n)) != HPN_OK || (rc = hpn_ctx_sync(ctx)) != HPN_OK)) die_hpn(ctx, rc, "hpn_memcpy_d2h");
-        t_copy += wall_s() - t0, t0 = wall_s();
-        if (!created) {      // (behind the first slice: everything the device needs has been allocated by now)
-            if (!writer.begin(o.out, head_blocks)) {
-                fputs(said.c_str(), stderr);
-                fputs("[bam_rmdup] fail to read/write input files\n", stderr);
-                leave(1);
-            }
-            created = true;
-        }
-        for (size_t k = 0; k < nb; ++k) writer.add(bytes.data() + blocks[k].off, blocks[k].len, blocks[k].crc, true);
-        n_blocks += nb;
-        t_hand += wall_s() - t0;
-        first += cnt;
-        if (last) break;
     }
     if (!writer.finish()) {
         fprintf(stderr, "[hpn] bam_rmdup: writing %s failed\n", o.out);
@@ -172,8 +120,8 @@ static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
         fprintf(stderr, "[hpn] bam_rmdup: inflate + record index %.3f s, classify + store %.3f s, groups + names + placement %.3f s, gather + cuts + crc %.3f s, "
                         "copies to the host %.3f s, handing to the writer %.3f s; %llu batches, %llu records in, %llu heads, %llu records out, %llu blocks; "
                         "writer: %.3f s deflating (all threads), %.3f s waited for\n",
-                t_ingest, t_store, t_decide, t_emit, t_copy, t_hand, (unsigned long long)n_batches, (unsigned long long)res.n_records,
-                (unsigned long long)res.n_heads, (unsigned long long)res.n_out, (unsigned long long)n_blocks, writer.deflate_seconds(), writer.waited_seconds());
+                t_ingest, t_store, t_decide, run.t_emit, run.t_copy, run.t_hand, (unsigned long long)n_batches, (unsigned long long)res.n_records,
+                (unsigned long long)res.n_heads, (unsigned long long)res.n_out, (unsigned long long)run.n_blocks, writer.deflate_seconds(), writer.waited_seconds());
     return 0;
 }
 

@@ -14,32 +14,16 @@
 // HPN_TIMING=1 says which route ran.
 #include <sys/stat.h>
 
-#include "../host/bam_gpu.hpp"
-#include "../host/bam_sort_host.hpp"
-#include "../host/report.hpp"
+#include "../host/bam_tool.hpp"
 
 using namespace hpn;
-
-#ifdef HPN_TEST_HOOKS
-static const uint64_t kSliceRecords = 1000;        // (the test-hooks build: the open block is carried over many slices)
-#else
-static const uint64_t kSliceRecords = 1u << 22;    // ~1 GB of payload per slice at 250 bytes a record
-#endif
 
 // 0 the output is written, 1 not for the device (the host route starts over; nothing has been said, no output is left)
 static int sort_device(hpn_ctx *ctx, const bamsort::Options &o, bool timing)
 {
     std::string said;
     bamsort::Header hdr;
-    {   // the header on the host: its text changes, and its blocks are the writer's first
-        FILE *f = fopen(o.in, "rb");
-        if (!f) return 1;
-        if (!bai::has_eof_marker(f)) said += "[bam_header_read] EOF marker is absent. The input is probably truncated.\n";
-        bai::BgzfSeq z(f);
-        const int hr = bamsort::read_header(z, hdr);
-        fclose(f);
-        if (hr != 0) return 1;
-    }
+    if (!open_bam_header(o.in, hdr, said)) return 1;   // on the host: its text changes, and its blocks are the writer's first
     bamsort::change_so(hdr.text, "coordinate");
     BgzfGpuStream bam;
     BamHeader parsed;
@@ -47,35 +31,24 @@ static int sort_device(hpn_ctx *ctx, const bamsort::Options &o, bool timing)
     bam.start();
     int rc = hpn_bam_sort_begin(ctx);
     if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_sort_begin");
-    double t_ingest = 0, t_store = 0, t_sort = 0, t_emit = 0, t_copy = 0, t_hand = 0, t0;
-    uint64_t n_batches = 0, n_blocks = 0;
-    bool empty_seen = false;
-    for (;;) {
-        hpn_raw_info info;
-        t0 = wall_s();
-        const int r = bam.next(&info);
-        t_ingest += wall_s() - t0;
-        if (r < 0) return 1;
-        if (r == 0) break;
-        const BgzfDevice &dev = bam.device();
-        if (!dev.n_blocks()) continue;
-        // a block of no bytes ends the stream for samtools' reader: only the file's last block may be one
-        if (empty_seen || dev.empty_blocks() > 1 || (dev.empty_blocks() == 1 && !dev.last_block_empty())) return 1;
-        empty_seen = dev.empty_blocks() != 0;
-        if (!info.n_records) continue;
+    double t_ingest = 0, t_store = 0, t_sort = 0, t0;
+    uint64_t n_batches = 0;
+    const bool fed = each_batch(bam, &t_ingest, [&](const BgzfDevice &) {
         hpn_bamsort_info si;
         t0 = wall_s();
         rc = hpn_bam_sort_add_raw_dev(ctx, bam.d_raw(), &si);
-        if (rc == HPN_E_NOMEM) return 1;                   // the working set does not fit the device
+        if (rc == HPN_E_NOMEM) return false;               // the working set does not fit the device
         if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_sort_add_raw_dev");
         t_store += wall_s() - t0, ++n_batches;
         if (si.bad_record >= 0) {
             if (timing)
                 fprintf(stderr, "[hpn] bam_sort: record %lld (refID %d, pos %d) is outside the device's domain (reason %u)\n", (long long)si.bad_record,
                         si.bad_tid, si.bad_pos, si.reason);
-            return 1;
+            return false;
         }
-    }
+        return true;
+    });
+    if (!fed) return 1;
     hpn_bamsort_result res;
     t0 = wall_s();
     rc = hpn_bam_sort_finish(ctx, &res);
@@ -101,50 +74,23 @@ static int sort_device(hpn_ctx *ctx, const bamsort::Options &o, bool timing)
     if (!bgzf_plain_blocks(head.data(), head.size(), level, head_blocks)) return 1;
     const std::string path = bamsort::output_path(o);
     BgzfWriter writer(level);
-    bool created = false;
-    auto give_up = [&]() {      // the output so far goes; the host route makes it again
-        if (created) {
-            writer.abandon();
-            if (!o.to_stdout) unlink(path.c_str());
+    SliceRun run;
+    const SliceCalls calls = {"hpn_bam_sort", hpn_bam_sort_emit, hpn_bam_sort_blocks, hpn_bam_sort_payload_dev, hpn_bam_sort_stored_dev};
+    // (what has gone to stdout cannot be taken back: behind the first slice the device's memory running out is an error there)
+    const int ws = write_slices(ctx, calls, res.n_records, level, writer, o.to_stdout, [&]() {
+        fputs(said.c_str(), stderr);
+        if (!parts.empty()) fprintf(stderr, "[bam_sort_core] merging from %d files...\n", (int)parts.size());
+        if (!writer.begin(path.c_str(), head_blocks)) {
+            if (!parts.empty()) fputs("[bam_merge_core2] fail to create the output file.\n", stderr);
+            return false;
         }
+        return true;
+    }, run);
+    if (ws == kSlicesNoOutput) return 0;
+    if (ws == kSlicesNoMem) {   // the output so far goes; the host route makes it again
+        if (run.created) writer.abandon();
+        if (run.created && !o.to_stdout) unlink(path.c_str());
         return 1;
-    };
-    std::vector<hpn_split_block> blocks;
-    std::vector<uint8_t> bytes;
-    for (uint64_t first = 0;;) {
-        const uint64_t cnt = res.n_records - first < kSliceRecords ? res.n_records - first : kSliceRecords;
-        const bool last = first + cnt == res.n_records;
-        hpn_split_info si;
-        t0 = wall_s();
-        rc = hpn_bam_sort_emit(ctx, first, cnt, last ? 1 : 0, &si);
-        if (rc == HPN_E_NOMEM && !(created && o.to_stdout)) return give_up();
-        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_sort_emit");
-        t_emit += wall_s() - t0, t0 = wall_s();
-        uint64_t nb = 0, n = 0;
-        const uint8_t *d = nullptr;
-        blocks.resize(si.n_blocks);
-        if ((rc = hpn_bam_sort_blocks(ctx, 0, blocks.data(), blocks.size(), &nb)) != HPN_OK) die_hpn(ctx, rc, "hpn_bam_sort_blocks");
-        rc = level == 0 ? hpn_bam_sort_stored_dev(ctx, &d, &n) : hpn_bam_sort_payload_dev(ctx, &d, &n);
-        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_sort_payload_dev");
-        bytes.resize(n);
-        if (n && ((rc = hpn_memcpy_d2h(ctx, bytes.data(), d, n)) != HPN_OK || (rc = hpn_ctx_sync(ctx)) != HPN_OK)) die_hpn(ctx, rc, "hpn_memcpy_d2h");
-        t_copy += wall_s() - t0, t0 = wall_s();
-        if (!created) {      // (behind the first slice: everything the device needs has been allocated by now)
-            fputs(said.c_str(), stderr);
-            if (!parts.empty()) fprintf(stderr, "[bam_sort_core] merging from %d files...\n", (int)parts.size());
-            if (!writer.begin(path.c_str(), head_blocks)) {
-                if (!parts.empty()) fputs("[bam_merge_core2] fail to create the output file.\n", stderr);
-                return 0;
-            }
-            created = true;
-        }
-        if (level == 0) writer.add_framed(bytes.data(), (size_t)n);
-        else
-            for (size_t k = 0; k < nb; ++k) writer.add(bytes.data() + blocks[k].off, blocks[k].len, blocks[k].crc, true);
-        n_blocks += nb;
-        t_hand += wall_s() - t0;
-        first += cnt;
-        if (last) break;
     }
     if (!writer.finish()) {
         fprintf(stderr, "bam_sort: writing %s failed\n", path.c_str());
@@ -154,8 +100,8 @@ static int sort_device(hpn_ctx *ctx, const bamsort::Options &o, bool timing)
         fprintf(stderr, "[hpn] bam_sort: inflate + record index %.3f s, keys + store %.3f s, sort + offsets %.3f s, gather + cuts + crc %.3f s, copies to the host "
                         "%.3f s, handing to the writer %.3f s; %llu batches, %llu records, %u key bits, %llu blocks; writer: %.3f s deflating (all threads), "
                         "%.3f s waited for\n",
-                t_ingest, t_store, t_sort, t_emit, t_copy, t_hand, (unsigned long long)n_batches, (unsigned long long)res.n_records, res.sort_bits,
-                (unsigned long long)n_blocks, writer.deflate_seconds(), writer.waited_seconds());
+                t_ingest, t_store, t_sort, run.t_emit, run.t_copy, run.t_hand, (unsigned long long)n_batches, (unsigned long long)res.n_records, res.sort_bits,
+                (unsigned long long)run.n_blocks, writer.deflate_seconds(), writer.waited_seconds());
     return 0;
 }
 
