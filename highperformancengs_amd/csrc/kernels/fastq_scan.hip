@@ -16,6 +16,7 @@
 // cost 3 % (scripts/k1_split.py, profiles/r01).
 // Bound: HBM read, 1 B per base + 8 B per record.  No MFMA: no contraction here.
 #include <stdlib.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -31,7 +32,9 @@ constexpr int kChunkTiles = 8;
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 
 // kSched: 0 = static grid-stride split, 1 = chunks from one counter, pair chunks last, 2 = ... pair chunks spread among the byte chunks
-template <int U, bool kNt, int kSched>
+// kOrigin: the byte tiles are counted from the last multiple of kOrigin bytes at or below the first byte of the range (128 = a
+// cache line, 4096 = one workgroup row), so every wave-instruction of a whole tile reads 1 KiB that starts ON a 128-byte line
+template <int U, bool kNt, int kSched, int kOrigin>
 __global__ __launch_bounds__(kScanThreads) void k_tally_scan(const uint8_t *__restrict__ qual,
                                                             const uint64_t *__restrict__ off, uint64_t n,
                                                             u64 *__restrict__ acc, u64 *__restrict__ sched)
@@ -43,15 +46,17 @@ __global__ __launch_bounds__(kScanThreads) void k_tally_scan(const uint8_t *__re
     const int tid = threadIdx.x;
     for (int i = tid; i <= HPN_LEN_BINS; i += kScanThreads) s_hist[i] = 0;
 
-    // ---- geometry: bytes [off[0], off[n]) as 16-byte vectors from an aligned base ----
+    // ---- geometry: bytes [off[0], off[n]) as 16-byte vectors from an origin aligned to kOrigin bytes ----
+    static_assert(kOrigin >= 16 && (kOrigin & (kOrigin - 1)) == 0 && kOrigin <= 16 * kTileVec, "the range starts inside tile 0");
     const uint64_t b0 = off[0], b1 = off[n];
     const uint64_t nbytes = b1 > b0 ? b1 - b0 : 0;
     const uint8_t *pbeg = qual + b0;
-    const int a0 = (int)((uintptr_t)pbeg & 15);
-    const u32 *vec = reinterpret_cast<const u32 *>(pbeg - a0);  // vector i = bytes [16i-a0, 16i-a0+16)
-    const uint64_t nv = nbytes ? (a0 + nbytes + 15) >> 4 : 0;
-    const uint64_t nvec = nv > 2 ? nv - 2 : 0;  // vectors 1 .. nv-2 are whole; first and last may be partial
-    const uint64_t btiles = (nvec + kTileVec - 1) / kTileVec;
+    const uint64_t a = (uintptr_t)pbeg & (uintptr_t)(kOrigin - 1);  // the range is bytes [a, a + nbytes) from the origin
+    const u32 *vec = reinterpret_cast<const u32 *>(pbeg - a);       // vector i = bytes [16i, 16i+16) from the origin
+    // whole vectors: [vlo, vhi).  In front of them at most one partial vector (vlo-1, when a is no multiple of 16), behind them
+    // at most one (vhi); vlo > vhi: the range lies inside ONE vector.  Nothing outside vectors vlo-1 .. vhi is ever loaded.
+    const uint64_t vlo = (a + 15) >> 4, vhi = (a + nbytes) >> 4;
+    const uint64_t btiles = vhi > vlo ? (vhi + kTileVec - 1) / kTileVec : 0;  // tile t = vectors [t kTileVec, (t+1) kTileVec)
     // off[] as pairs {off[e], off[e+1]} from the first 16-byte aligned element e0
     const uint64_t e0 = ((uintptr_t)off >> 3) & 1;
     const u64x2 *pairs = reinterpret_cast<const u64x2 *>(off + e0);
@@ -63,16 +68,16 @@ __global__ __launch_bounds__(kScanThreads) void k_tally_scan(const uint8_t *__re
     auto ld = [](const u32 *p) { return kNt ? __builtin_nontemporal_load(p) : *p; };
 
     auto byte_tile = [&](uint64_t t) {
-        const uint64_t base = 1 + t * kTileVec + tid;
+        const uint64_t base = t * kTileVec + tid;
         u32 v[U];
-        if ((t + 1) * kTileVec <= nvec) {
+        if (t * kTileVec >= vlo && (t + 1) * kTileVec <= vhi) {  // a whole tile: every wave-instruction reads eight whole lines
 #pragma unroll
             for (int k = 0; k < U; ++k) v[k] = ld(vec + base + (uint64_t)k * kScanThreads);
-        } else {
+        } else {  // the range's first and last tile
 #pragma unroll
             for (int k = 0; k < U; ++k) {
                 const uint64_t idx = base + (uint64_t)k * kScanThreads;
-                v[k] = idx < nv - 1 ? ld(vec + idx) : u32{0, 0, 0, 0};
+                v[k] = idx >= vlo && idx < vhi ? ld(vec + idx) : u32{0, 0, 0, 0};
             }
         }
 #pragma unroll
@@ -199,10 +204,13 @@ __global__ __launch_bounds__(kScanThreads) void k_tally_scan(const uint8_t *__re
     }
 
     if (blockIdx.x == 0 && tid == 0) {
-        if (nv) {  // the two possibly partial vectors at the ends of the byte range
-            const int e = (int)min((uint64_t)16, (uint64_t)a0 + nbytes);
-            swar16(mask_bytes(vec[0], a0, e), c20, c30, hi);
-            if (nv > 1) swar16(mask_bytes(vec[nv - 1], 0, (int)((a0 + nbytes) - ((nv - 1) << 4))), c20, c30, hi);
+        // the partial vectors at the ends of the byte range
+        const int ah = (int)(a & 15), at = (int)((a + nbytes) & 15);
+        if (nbytes && vlo > vhi) {  // the whole range inside one vector
+            swar16(mask_bytes(vec[vhi], ah, ah + (int)nbytes), c20, c30, hi);
+        } else if (nbytes) {
+            if (ah) swar16(mask_bytes(vec[vlo - 1], ah, 16), c20, c30, hi);
+            if (at) swar16(mask_bytes(vec[vhi], 0, at), c20, c30, hi);
         }
         if (e0 && n) {  // record 0 sits in front of the first aligned pair
             const uint64_t len = off[1] - off[0];
@@ -243,27 +251,35 @@ __global__ __launch_bounds__(kScanThreads) void k_tally_scan(const uint8_t *__re
     }
 }
 
+// The origin the byte tiles are counted from in what ships (same-session A/B of 128 against 4096: docs/kernels/k1_tally_scan.md).
+constexpr int kK1Origin = 128;
+
 // Tuning knobs for A/B runs (test-hooks builds; scripts/k1_sweep.py): HPN_K1_VARIANT = unroll*100 + nt*10 + sched
-// (default 811: 8 loads in flight, non-temporal, dynamic chunks with the pair chunks last; ..2: pair chunks spread out), HPN_K1_WG_PER_CU.
+// (default 811: 8 loads in flight, non-temporal, dynamic chunks with the pair chunks last; ..2: pair chunks spread out), optionally
+// followed by @origin (811@4096; 128 or 4096, anything else is an error like an unknown variant), HPN_K1_WG_PER_CU.
 hipError_t launch_tally_scan(const uint8_t *d_qual, const uint64_t *d_off, uint64_t n, uint64_t approx_bytes,
                              u64 *d_acc, u64 *d_sched, int n_cu, hipStream_t st)
 {
     const char *ev = test_env("HPN_K1_VARIANT"), *eg = test_env("HPN_K1_WG_PER_CU");
     const int variant = ev ? atoi(ev) : 811;
+    const char *eo = ev ? strchr(ev, '@') : nullptr;
+    const int origin = eo ? atoi(eo + 1) : kK1Origin;
+    if (origin != 128 && origin != 4096) return hipErrorInvalidValue;
     const int unroll = variant / 100;
     // workgroups (4 waves each) per CU.  Long launches: 2 -- same-session sweep over 158 GB: 2 -> 24.01 ms, 3 -> 24.35,
     // 4 -> 24.51, 6 -> 24.63, 8/16 slower still (profiles/r01e/k1_sweep_wg.txt; a loads-only kernel reads 6.6-6.9 TB/s
     // with 2 per CU, 6.3-6.4 with 4: profiles/r01e/hbm_read_ubench.txt).  Short launches keep 4 for the latency.
     const uint64_t per_cu = eg ? (uint64_t)atoi(eg) : (approx_bytes >= (1ull << 30) ? 2 : 4);
     if (unroll <= 0) return hipErrorInvalidValue;
-    const uint64_t tiles = approx_bytes / (16ull * kScanThreads * unroll) + n / (2 * kPairTile) + 2;
+    const uint64_t tiles = approx_bytes / (16ull * kScanThreads * unroll) + n / (2 * kPairTile) + 3;  // (the range may start inside tile 0)
     const uint64_t want = (variant % 10) ? (tiles + kChunkTiles - 1) / kChunkTiles : tiles;
     const uint64_t cap = (uint64_t)n_cu * per_cu;
     const dim3 grid((unsigned)(want < cap ? want : cap)), block(kScanThreads);
     switch (variant) {
 #define HPN_K1(U, NT, DYN) \
     case U * 100 + NT * 10 + DYN: \
-        hipLaunchKernelGGL((k_tally_scan<U, NT, DYN>), grid, block, 0, st, d_qual, d_off, n, d_acc, d_sched); \
+        if (origin == 128) hipLaunchKernelGGL((k_tally_scan<U, NT, DYN, 128>), grid, block, 0, st, d_qual, d_off, n, d_acc, d_sched); \
+        else hipLaunchKernelGGL((k_tally_scan<U, NT, DYN, 4096>), grid, block, 0, st, d_qual, d_off, n, d_acc, d_sched); \
         break;
         HPN_K1(4, 1, 0) HPN_K1(4, 1, 1) HPN_K1(8, 0, 0) HPN_K1(8, 0, 1) HPN_K1(8, 1, 0) HPN_K1(8, 1, 1) HPN_K1(8, 1, 2) HPN_K1(16, 1, 0)
         HPN_K1(16, 1, 1)
