@@ -179,6 +179,16 @@ class BamSortResult(C.Structure):
                 ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("sort_bits", C.c_uint32)]
 
 
+class BamMergeInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
+                ("reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BamMergeResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_files", C.c_uint64), ("payload_bytes", C.c_uint64), ("n_lifted", C.c_uint64), ("bad_record", C.c_int64),
+                ("bad_tid", C.c_int32), ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("sort_bits", C.c_uint32)]
+
+
 class RmdupInfo(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
                 ("reason", C.c_uint32), ("reserved", C.c_uint32)]
@@ -328,6 +338,15 @@ SYMBOLS = [
     ("hpn_bam_sort_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_bam_sort_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_sort_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_merge_begin", _int, [_vp]),
+    ("hpn_bam_merge_next_file", _int, [_vp]),
+    ("hpn_bam_merge_add_raw_dev", _int, [_vp, _vp, C.POINTER(BamMergeInfo)]),
+    ("hpn_bam_merge_finish", _int, [_vp, C.POINTER(BamMergeResult)]),
+    ("hpn_bam_merge_order", _int, [_vp, _vp, _u64]),
+    ("hpn_bam_merge_emit", _int, [_vp, _u64, _u64, _int, C.POINTER(SplitInfo)]),
+    ("hpn_bam_merge_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_bam_merge_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_merge_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_rmdup_begin", _int, [_vp, _i32, _u32, _vp, _vp, _u32]),
     ("hpn_bam_rmdup_add_raw_dev", _int, [_vp, _vp, C.POINTER(RmdupInfo)]),
     ("hpn_bam_rmdup_finish", _int, [_vp, C.POINTER(RmdupResult)]),
@@ -383,7 +402,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 15:
+    if L.hpn_abi_version() != 16:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

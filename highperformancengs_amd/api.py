@@ -929,6 +929,50 @@ class Context:
         """The closed blocks of the last bam_rmdup_emit framed as stored BGZF blocks (level 0), copied to the host."""
         return self._dev_span_bytes("hpn_bam_rmdup_stored_dev")
 
+    # ---- samtools merge: several BAMs merged into one (hpn_bam_merge_*) ----
+    def bam_merge_begin(self):
+        self._ck(self.L.hpn_bam_merge_begin(self.h), "hpn_bam_merge_begin")
+
+    def bam_merge_next_file(self):
+        """The batches that follow belong to the next input file (a file of no batches is legal)."""
+        self._ck(self.L.hpn_bam_merge_next_file(self.h), "hpn_bam_merge_next_file")
+
+    def bam_merge_add_raw_dev(self, d_raw):
+        """The batch hpn_bam_raw_index_dev indexed last goes into the session's record store (d_raw None: no records) -> BamMergeInfo."""
+        info = _lib.BamMergeInfo()
+        self._ck(self.L.hpn_bam_merge_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), "hpn_bam_merge_add_raw_dev")
+        return info
+
+    def bam_merge_finish(self):
+        """Merges -> BamMergeResult (n_records, n_files, payload_bytes, n_lifted, the first record outside the domain, sort_bits)."""
+        res = _lib.BamMergeResult()
+        self._ck(self.L.hpn_bam_merge_finish(self.h, C.byref(res)), "hpn_bam_merge_finish")
+        return res
+
+    def bam_merge_order(self, n):
+        """order[j]: the session ordinal of the j-th record of the output."""
+        out = np.zeros(int(n), np.uint32)
+        self._ck(self.L.hpn_bam_merge_order(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_merge_order")
+        return out
+
+    def bam_merge_emit(self, first_record, max_records, last=False):
+        """The next slice of the merged records: gathered, cut, every closed block with its CRC-32 -> SplitInfo."""
+        info = _lib.SplitInfo()
+        self._ck(self.L.hpn_bam_merge_emit(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), "hpn_bam_merge_emit")
+        return info
+
+    def bam_merge_blocks(self, n):
+        """The n closed blocks of the last bam_merge_emit -> list of SplitBlock (off, len, crc, tid)."""
+        return self._last_blocks("hpn_bam_merge_blocks", n)
+
+    def bam_merge_payload(self):
+        """The payload buffer of the last bam_merge_emit up to the end of its last closed block, copied to the host."""
+        return self._dev_span_bytes("hpn_bam_merge_payload_dev")
+
+    def bam_merge_stored(self):
+        """The closed blocks of the last bam_merge_emit framed as stored BGZF blocks (level 0), copied to the host."""
+        return self._dev_span_bytes("hpn_bam_merge_stored_dev")
+
     # ---- collectives / synthetic -----------------------------------------
     def comm_init(self, rank, n_ranks, unique_id: bytes):
         buf = (C.c_uint8 * _lib.UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

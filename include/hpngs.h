@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 15
+#define HPN_ABI_VERSION 16
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -1187,6 +1187,50 @@ int hpn_bam_rmdup_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records
 int hpn_bam_rmdup_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
 int hpn_bam_rmdup_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
 int hpn_bam_rmdup_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
+
+/* ---- samtools merge: several BAMs merged into one ------------------------------------------------
+ * bam_sort.c (samtools-0.1.19), bam_merge_core2, for the order by coordinate: a heap over one record per input file, ordered by
+ * (uint64_t)refID << 32 | (uint32_t)(pos + 1) << 1 | strand (strand: flag 0x10; the low word is cut to 32 bits, so every pos has
+ * its key), ties to the lower file number.  The reference never checks that its inputs are sorted; for any inputs what the heap
+ * writes is the records, file after file in argument order, sorted stably by their EFFECTIVE key: the largest key of the
+ * record's own file up to and including the record.  The session computes exactly that, and cuts the result into BGZF blocks by
+ * bam_write1's rule (see hpn_bam_split_*).  (docs/kernels/bam_merge.md)
+ *   hpn_bam_merge_begin()
+ *   per input file, in argument order: hpn_bam_merge_next_file() -- it closes the file before it; a file of no records is legal --
+ *   then per batch of that file: hpn_bam_raw_index_dev(...), then hpn_bam_merge_add_raw_dev(d_raw, &info): the batch's records
+ *              are copied into the session's record store on the device (d_raw may be reused afterwards); d_raw NULL: no records
+ *   hpn_bam_merge_finish(&res)            merges; res.n_files: the hpn_bam_merge_next_file calls, res.payload_bytes: the records'
+ *                                         bytes, res.n_lifted: the records whose effective key is not their own -- 0 exactly
+ *                                         when every file was sorted by the heap's key
+ *   hpn_bam_merge_order(order, n)         order[j]: the session ordinal (files in argument order, records in file order) of the
+ *                                         j-th record of the output (n = res.n_records)
+ *   hpn_bam_merge_emit / _blocks / _payload_dev / _stored_dev    as hpn_bam_sort_emit and its three readers
+ * Domain: no record with the key 2^64 - 1 (refID -1, reverse strand, pos -2 or 2^31 - 2: the heap's HEAP_EMPTY, where the
+ * reference ends its output) and fewer than 2^31 records.  The first record outside it is reported -- bad_record (session
+ * ordinal, -1: none), bad_tid, bad_pos, reason (1 the HEAP_EMPTY key, 2 the 2^31-th record) -- and nothing is merged: the caller
+ * merges on the host (csrc/host/bam_merge_host.hpp).  A call out of this order returns HPN_E_STATE.  Synchronous. */
+typedef struct hpn_bammerge_info {
+    uint64_t n_records;      /* records of this batch */
+    uint64_t store_bytes;    /* bytes the record store holds after this call */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, reserved;
+} hpn_bammerge_info;
+typedef struct hpn_bammerge_result {
+    uint64_t n_records, n_files, payload_bytes, n_lifted;
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, sort_bits; /* sort_bits: the key bits [0, sort_bits) the radix sort ran over */
+} hpn_bammerge_result;
+int hpn_bam_merge_begin(hpn_ctx *ctx);
+int hpn_bam_merge_next_file(hpn_ctx *ctx);
+int hpn_bam_merge_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw, hpn_bammerge_info *info);
+int hpn_bam_merge_finish(hpn_ctx *ctx, hpn_bammerge_result *res);
+int hpn_bam_merge_order(hpn_ctx *ctx, uint32_t *order, uint64_t n);
+int hpn_bam_merge_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info);
+int hpn_bam_merge_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
+int hpn_bam_merge_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
+int hpn_bam_merge_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
 
 /* ---- multi-GPU reduction of count vectors -----------------------------------
  * One RCCL communicator per context; `unique_id` is the 128-byte ncclUniqueId
