@@ -189,6 +189,17 @@ class BamMergeResult(C.Structure):
                 ("bad_tid", C.c_int32), ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("sort_bits", C.c_uint32)]
 
 
+class FixmateInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
+                ("reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FixmateResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_out", C.c_uint64), ("n_pairs", C.c_uint64), ("n_singletons", C.c_uint64), ("n_tags", C.c_uint64),
+                ("bytes_added", C.c_uint64), ("payload_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
+                ("reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class RmdupInfo(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
                 ("reason", C.c_uint32), ("reserved", C.c_uint32)]
@@ -347,6 +358,14 @@ SYMBOLS = [
     ("hpn_bam_merge_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_bam_merge_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_merge_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_fixmate_begin", _int, [_vp, _int, _i32, _vp]),
+    ("hpn_bam_fixmate_add_raw_dev", _int, [_vp, _vp, C.POINTER(FixmateInfo)]),
+    ("hpn_bam_fixmate_finish", _int, [_vp, C.POINTER(FixmateResult)]),
+    ("hpn_bam_fixmate_order", _int, [_vp, _vp, _u64]),
+    ("hpn_bam_fixmate_emit", _int, [_vp, _u64, _u64, _int, C.POINTER(SplitInfo)]),
+    ("hpn_bam_fixmate_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_bam_fixmate_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_fixmate_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_rmdup_begin", _int, [_vp, _i32, _u32, _vp, _vp, _u32]),
     ("hpn_bam_rmdup_add_raw_dev", _int, [_vp, _vp, C.POINTER(RmdupInfo)]),
     ("hpn_bam_rmdup_finish", _int, [_vp, C.POINTER(RmdupResult)]),
@@ -402,7 +421,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 16:
+    if L.hpn_abi_version() != 17:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

@@ -973,6 +973,48 @@ class Context:
         """The closed blocks of the last bam_merge_emit framed as stored BGZF blocks (level 0), copied to the host."""
         return self._dev_span_bytes("hpn_bam_merge_stored_dev")
 
+    # ---- samtools fixmate: mate fields of a name-grouped BAM filled in (hpn_bam_fixmate_*) ----
+    def bam_fixmate_begin(self, remove_reads, target_len):
+        """target_len: the header's l_ref values; remove_reads: -r, records without a refID and secondary ones are dropped."""
+        tl = np.ascontiguousarray(target_len, dtype=np.uint32)
+        self._ck(self.L.hpn_bam_fixmate_begin(self.h, 1 if remove_reads else 0, int(tl.size), _ptr(tl) if tl.size else None), "hpn_bam_fixmate_begin")
+
+    def bam_fixmate_add_raw_dev(self, d_raw):
+        """The batch hpn_bam_raw_index_dev indexed last goes into the session's record store (d_raw None: no records) -> FixmateInfo."""
+        info = _lib.FixmateInfo()
+        self._ck(self.L.hpn_bam_fixmate_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), "hpn_bam_fixmate_add_raw_dev")
+        return info
+
+    def bam_fixmate_finish(self):
+        """Decides -> FixmateResult (records in and out, pairs, singletons, CT fields, bytes added, the first record outside the domain)."""
+        res = _lib.FixmateResult()
+        self._ck(self.L.hpn_bam_fixmate_finish(self.h, C.byref(res)), "hpn_bam_fixmate_finish")
+        return res
+
+    def bam_fixmate_order(self, n):
+        """order[j]: the session ordinal of the j-th record of the output."""
+        out = np.zeros(int(n), np.uint32)
+        self._ck(self.L.hpn_bam_fixmate_order(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_fixmate_order")
+        return out
+
+    def bam_fixmate_emit(self, first_record, max_records, last=False):
+        """The next slice of the output: gathered, rewritten, cut, every closed block with its CRC-32 -> SplitInfo."""
+        info = _lib.SplitInfo()
+        self._ck(self.L.hpn_bam_fixmate_emit(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), "hpn_bam_fixmate_emit")
+        return info
+
+    def bam_fixmate_blocks(self, n):
+        """The n closed blocks of the last bam_fixmate_emit -> list of SplitBlock (off, len, crc, tid)."""
+        return self._last_blocks("hpn_bam_fixmate_blocks", n)
+
+    def bam_fixmate_payload(self):
+        """The payload buffer of the last bam_fixmate_emit up to the end of its last closed block, copied to the host."""
+        return self._dev_span_bytes("hpn_bam_fixmate_payload_dev")
+
+    def bam_fixmate_stored(self):
+        """The closed blocks of the last bam_fixmate_emit framed as stored BGZF blocks (level 0), copied to the host."""
+        return self._dev_span_bytes("hpn_bam_fixmate_stored_dev")
+
     # ---- collectives / synthetic -----------------------------------------
     def comm_init(self, rank, n_ranks, unique_id: bytes):
         buf = (C.c_uint8 * _lib.UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

@@ -2,7 +2,10 @@
 //   BadRecord   the first record outside a family's domain, fetched and reported in one place (split, bai, sort, rmdup);
 //   BamStore    the records of every batch behind one another on the device, with each one's size and place (sort, rmdup);
 //   SliceOut    the stored records in the order a family decided, handed back slice by slice: gathered behind the block the
-//               slice before left open, cut as bam_write1 would, CRC-32, for level 0 the stored image (sort, rmdup).
+//               slice before left open, cut as bam_write1 would, CRC-32, for level 0 the stored image (sort, rmdup).  A family
+//               whose output records are not the stored ones byte for byte (fixmate) gives `extra` -- output record j takes
+//               size[order[j]] + extra[order[j]] bytes -- and `patch`, which runs on the gathered slice in front of the cuts and
+//               the CRC-32; without the two the slices are what they were.
 // A family writes its per-record kernel (size[], soff[] and info words [0..2] as k_sort_keys fills them), its _finish and its
 // order array.  Plain movable values: a session resets by assigning fresh ones.
 #pragma once
@@ -79,6 +82,13 @@ struct SliceOut {
     bool ended = false, stored_made = false;
     std::vector<hpn_split_block> list;   // the closed blocks of the last sliceout_emit
     uint64_t payload_bytes = 0, stored_bytes = 0;
+    // by stored ordinal: the bytes a record grows by behind its stored ones (nullptr: none), `grown` their sum over the output
+    const uint32_t *extra = nullptr;
+    uint64_t grown = 0;
+    // the slice's records [first, first + cnt) lie gathered at pay, record first + k at out_off[first + k] - out_off[first]:
+    // rewrite them in place, on the context's stream (nullptr: they stay as the store has them)
+    int (*patch)(hpn_ctx *c, void *arg, const uint32_t *order, const u64 *out_off, uint64_t first, uint64_t cnt, uint8_t *pay) = nullptr;
+    void *patch_arg = nullptr;
 };
 
 inline int sliceout_begin(hpn_ctx *c, SliceOut &o)
@@ -94,18 +104,19 @@ inline int sliceout_reserve(hpn_ctx *c, SliceOut &o, uint64_t n_in)      // room
 }
 
 // out_off[j]: where output record j = stored record order[j] starts in the output's payload; out_off[n_out] = o.payload, which is
-// the store's length (exact) or no more than it.  sliceout_reserve has been called.
+// the store's length and what the records grow by (exact) or no more than it.  sliceout_reserve has been called.
 inline int sliceout_offsets(hpn_ctx *c, SliceOut &o, const BamStore &st, const uint32_t *order, uint64_t n_out, bool exact, const char *who)
 {
-    HPN_HIP(c, launch_bamsort_psize((const uint32_t *)st.size.p, order, n_out, (uint32_t *)o.psize.p, c->stream));
+    if (o.extra) HPN_HIP(c, launch_bamsort_psize_grown((const uint32_t *)st.size.p, o.extra, order, n_out, (uint32_t *)o.psize.p, c->stream));
+    else HPN_HIP(c, launch_bamsort_psize((const uint32_t *)st.size.p, order, n_out, (uint32_t *)o.psize.p, c->stream));
     HPN_HIP(c, hipStreamSynchronize(c->stream));
     const int rc = hpn_excl_scan(c, n_out ? o.psize.p : nullptr, 32, o.out_off.p, 64, n_out);
     if (rc != HPN_OK) return rc;
     HPN_HIP(c, hipMemcpyAsync(&o.payload, (const u64 *)o.out_off.p + n_out, 8, hipMemcpyDeviceToHost, c->stream));
     HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (exact ? o.payload != st.len : o.payload > st.len)
+    if (exact ? o.payload != st.len + o.grown : o.payload > st.len + o.grown)
         return fail(c, HPN_E_HIP, "%s: the %s records take %llu bytes, the store holds %llu", who, exact ? "sorted" : "surviving", (unsigned long long)o.payload,
-                    (unsigned long long)st.len);
+                    (unsigned long long)(st.len + o.grown));
     return HPN_OK;
 }
 
@@ -149,6 +160,7 @@ inline int sliceout_emit(hpn_ctx *c, SliceOut &o, const BamStore &st, const uint
                                      first_record, cnt, (uint8_t *)o.pay.p + o.fill, c->n_cu, c->stream));
     HPN_HIP(c, hipEventRecord(c->ev_end[kFamTrim], c->stream));
     c->ev_valid[kFamTrim] = true;
+    if (o.patch && cnt && (rc = o.patch(c, o.patch_arg, order, (const u64 *)o.out_off.p, first_record, cnt, (uint8_t *)o.pay.p + o.fill)) != HPN_OK) return rc;
     HPN_HIP(c, hipStreamSynchronize(c->stream));       // (`init` is this call's)
     if ((rc = cut_blocks(c, o.cw, (const u64 *)o.Q.p, (const uint32_t *)o.ikey.p, m, 1, (u64 *)o.cut_info.p, total, o.list, who)) != HPN_OK) return rc;
     int32_t open_tid = -1;

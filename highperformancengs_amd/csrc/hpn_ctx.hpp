@@ -48,13 +48,13 @@ struct Scratch {
     }
 };
 
-// What a session family (hpn_fastq_uniq_*, ..., hpn_bam_split_*, hpn_bam_bai_*, hpn_bam_sort_*, hpn_bam_rmdup_*, hpn_bam_merge_*) keeps between its calls: the context owns one per family, made
+// What a session family (hpn_fastq_uniq_*, ..., hpn_bam_split_*, hpn_bam_bai_*, hpn_bam_sort_*, hpn_bam_rmdup_*, hpn_bam_merge_*, hpn_bam_fixmate_*) keeps between its calls: the context owns one per family, made
 // on first use.  A family's state names its slot as `kSlot`; a new family adds its slot here and nothing else outside its file.
 // (What the BAM families share -- BadRecord, the record store, the slices -- they hold as values: hpn_bamrec.hpp.)
 struct FamilyState {
     virtual ~FamilyState() = default;
 };
-enum { kStUniq = 0, kStSort, kStUniqq, kStUsort, kStTwobit, kStPair, kStMrle, kStRfastqc, kStSplit, kStKseq, kStBai, kStBamSort, kStBamRmdup, kStBamMerge, kStCount };
+enum { kStUniq = 0, kStSort, kStUniqq, kStUsort, kStTwobit, kStPair, kStMrle, kStRfastqc, kStSplit, kStKseq, kStBai, kStBamSort, kStBamRmdup, kStBamMerge, kStBamFixmate, kStCount };
 
 enum { kFamTally = 0, kFamTrim = 1, kFamDepth = 2, kFamWindow = 3, kFamText = 4, kFamInflate = 5, kFamRaw = 6, kFamRawFields = 7, kFamCount = 8 };
 

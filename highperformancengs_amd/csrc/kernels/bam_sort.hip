@@ -9,7 +9,7 @@
 //                   -1 <= pos <= 2^30 - 2 through one atomicMin
 //   k_sort_rank     the high words -> ranks that keep their unsigned order: refIDs from 0 up count from the smallest one, the
 //                   negative ones (-1, and strays below it) follow from their smallest; the largest key for the bit range
-//   k_sort_psize    psize[j] = size[order[j]]
+//   k_sort_psize    psize[j] = size[order[j]]   (k_sort_psize_grown: + extra[order[j]], for records that grow on their way out)
 //   k_sort_items    a slice of the sorted records as the items of the cut kernels (kernels/bam_split.hip): Q and key
 //   k_sort_gather   16 lanes a record: record order[j] from the store to its place in the slice's payload
 #include "bam_sort.hpp"
@@ -121,6 +121,13 @@ __global__ __launch_bounds__(kBsThreads) void k_sort_psize(const uint32_t *__res
     if (j < n) psize[j] = size[order[j]];
 }
 
+__global__ __launch_bounds__(kBsThreads) void k_sort_psize_grown(const uint32_t *__restrict__ size, const uint32_t *__restrict__ extra,
+                                                                 const uint32_t *__restrict__ order, uint64_t n, uint32_t *__restrict__ psize)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * kBsThreads + threadIdx.x;
+    if (j < n) psize[j] = size[order[j]] + extra[order[j]];
+}
+
 // items of the slice [first, first + cnt) of the sorted records: item 0 the open block's `fill` bytes, item i + 1 record first + i
 __global__ __launch_bounds__(kBsThreads) void k_sort_items(const u64 *__restrict__ out_off, uint64_t first, uint64_t cnt, uint32_t fill,
                                                            uint32_t open_key, u64 *__restrict__ Q, uint32_t *__restrict__ key)
@@ -206,6 +213,13 @@ hipError_t launch_bamsort_psize(const uint32_t *size, const uint32_t *order, uin
 {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_sort_psize, dim3(bs_grid(n)), dim3(kBsThreads), 0, st, size, order, n, psize);
+    return hipGetLastError();
+}
+
+hipError_t launch_bamsort_psize_grown(const uint32_t *size, const uint32_t *extra, const uint32_t *order, uint64_t n, uint32_t *psize, hipStream_t st)
+{
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_sort_psize_grown, dim3(bs_grid(n)), dim3(kBsThreads), 0, st, size, extra, order, n, psize);
     return hipGetLastError();
 }
 

@@ -18,6 +18,8 @@ hipError_t launch_bamsort_keys(const uint8_t *raw, const uint64_t *rec_off, uint
                                uint32_t *size, u64 *soff, u64 *info, hipStream_t st);
 hipError_t launch_bamsort_rank(u64 *key, uint64_t n, u64 *info, hipStream_t st);
 hipError_t launch_bamsort_psize(const uint32_t *size, const uint32_t *order, uint64_t n, uint32_t *psize, hipStream_t st);
+// psize[j] = size[order[j]] + extra[order[j]]: a family whose records grow on their way out (hpn_bamrec.hpp: SliceOut::extra)
+hipError_t launch_bamsort_psize_grown(const uint32_t *size, const uint32_t *extra, const uint32_t *order, uint64_t n, uint32_t *psize, hipStream_t st);
 hipError_t launch_bamsort_items(const u64 *out_off, uint64_t first, uint64_t cnt, uint32_t fill, uint32_t open_key, u64 *Q, uint32_t *key, hipStream_t st);
 hipError_t launch_bamsort_gather(const uint8_t *store, const u64 *soff, const uint32_t *size, const uint32_t *order, const u64 *out_off, uint64_t first,
                                  uint64_t cnt, uint8_t *pay, int n_cu, hipStream_t st);

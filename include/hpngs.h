@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 16
+#define HPN_ABI_VERSION 17
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -1231,6 +1231,53 @@ int hpn_bam_merge_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records
 int hpn_bam_merge_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
 int hpn_bam_merge_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
 int hpn_bam_merge_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
+
+/* ---- samtools fixmate: mate fields of a name-grouped BAM filled in -------------------------------
+ * bam_mate.c (samtools-0.1.19), bam_mating_core: over the records in file order with one pending record.  A record with
+ * refID < 0 is written at once (dropped with remove_reads); otherwise flag 0x4 is set where bam_calend lies beyond the target's
+ * length, and a record with flag 0x100 is written at once (dropped with remove_reads).  Every other record is LIVE: two live
+ * records in a row with the same name are a pair -- both get the other's refID and pos as mate fields, the insert size from the
+ * 5' ends (0 unless both lie on one target and neither has 0x4 or 0x8), 0x20 from the other's 0x10, 0x8 without 0x2 where the
+ * other has 0x4, and on one target the record with the smaller pos gets a CT:Z field appended (bam_template_cigar) --, a live
+ * record followed by another name is a singleton (mate fields -1, -1, 0; with 0x1: 0x8 set, 0x20 and 0x2 cleared), and the
+ * pending record at the end of the file is written as it is.  The output's order is not the input's: a skipped record is written
+ * in front of a pending one that came earlier.  (docs/kernels/bam_fixmate.md)
+ *   hpn_bam_fixmate_begin(remove_reads, n_targets, target_len)      the header's l_ref values (copied)
+ *   per batch: hpn_bam_raw_index_dev(...), then hpn_bam_fixmate_add_raw_dev(d_raw, &info): the batch's records are copied into
+ *              the session's record store on the device (d_raw may be reused afterwards); d_raw NULL: no records.  A pair may lie
+ *              in two batches.
+ *   hpn_bam_fixmate_finish(&res)          decides; res.n_out records leave, res.payload_bytes their bytes (bytes_added of them CT
+ *                                         fields, n_tags of them)
+ *   hpn_bam_fixmate_order(order, n)       order[j]: the session ordinal of the j-th record of the output (n = res.n_out)
+ *   hpn_bam_fixmate_emit / _blocks / _payload_dev / _stored_dev    as hpn_bam_sort_emit and its three readers; the records of a
+ *                                         slice are rewritten (five core fields, the CT field) before they are cut and summed
+ * Domain: CIGAR ops 0..8 (reason 1), live records' names with their first NUL as their last byte (2), refID < n_targets (3), a
+ * name and CIGAR inside the record (4), fewer than 2^31 records (5).  The first record outside it is reported -- bad_record
+ * (session ordinal, -1: none), bad_tid, bad_pos, reason -- and nothing is fixed: the caller works on the host
+ * (csrc/host/bam_fixmate_host.hpp).  A call out of this order returns HPN_E_STATE.  Synchronous. */
+typedef struct hpn_fixmate_info {
+    uint64_t n_records;      /* records of this batch */
+    uint64_t store_bytes;    /* bytes the record store holds after this call */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, reserved;
+} hpn_fixmate_info;
+typedef struct hpn_fixmate_result {
+    uint64_t n_records, n_out;                  /* records in, records out */
+    uint64_t n_pairs, n_singletons, n_tags;     /* pairs, singletons (the pending record at the end is none), CT fields */
+    uint64_t bytes_added, payload_bytes;
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, reserved;
+} hpn_fixmate_result;
+int hpn_bam_fixmate_begin(hpn_ctx *ctx, int remove_reads, int32_t n_targets, const uint32_t *target_len);
+int hpn_bam_fixmate_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw, hpn_fixmate_info *info);
+int hpn_bam_fixmate_finish(hpn_ctx *ctx, hpn_fixmate_result *res);
+int hpn_bam_fixmate_order(hpn_ctx *ctx, uint32_t *order, uint64_t n);
+int hpn_bam_fixmate_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info);
+int hpn_bam_fixmate_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
+int hpn_bam_fixmate_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
+int hpn_bam_fixmate_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
 
 /* ---- multi-GPU reduction of count vectors -----------------------------------
  * One RCCL communicator per context; `unique_id` is the 128-byte ncclUniqueId
