@@ -750,7 +750,28 @@ class Context:
         """The n closed blocks of the last split_add_raw_dev -> ctypes array of SplitBlock (off, len, crc, tid)."""
         return self._last_blocks("hpn_bam_split_blocks", n)
 
-    # what the sessions that write BAM blocks (split, sort, rmdup) answer alike, by the C function's name
+    # what the record-store sessions (sort, rmdup, merge, fixmate) take and answer alike, by the C function's name
+    def _raw_add(self, name, Info, d_raw):
+        info = Info()
+        self._ck(getattr(self.L, name)(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), name)
+        return info
+
+    def _finish(self, name, Result):
+        res = Result()
+        self._ck(getattr(self.L, name)(self.h, C.byref(res)), name)
+        return res
+
+    def _order(self, name, n):
+        out = np.zeros(int(n), np.uint32)
+        self._ck(getattr(self.L, name)(self.h, _ptr(out) if n else None, int(n)), name)
+        return out
+
+    def _emit(self, name, first_record, max_records, last):
+        info = _lib.SplitInfo()
+        self._ck(getattr(self.L, name)(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), name)
+        return info
+
+    # what the sessions that write BAM blocks (split and those four) answer alike, by the C function's name
     def _last_blocks(self, name, n):
         out = (_lib.SplitBlock * max(int(n), 1))()
         got = C.c_uint64(0)
@@ -827,21 +848,15 @@ class Context:
 
     def bam_sort_add_raw_dev(self, d_raw):
         """The batch hpn_bam_raw_index_dev indexed last goes into the session's record store (d_raw None: no records) -> BamSortInfo."""
-        info = _lib.BamSortInfo()
-        self._ck(self.L.hpn_bam_sort_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), "hpn_bam_sort_add_raw_dev")
-        return info
+        return self._raw_add("hpn_bam_sort_add_raw_dev", _lib.BamSortInfo, d_raw)
 
     def bam_sort_finish(self):
         """Sorts -> BamSortResult (n_records, payload_bytes, fresh_mem, the first record outside the domain, sort_bits)."""
-        res = _lib.BamSortResult()
-        self._ck(self.L.hpn_bam_sort_finish(self.h, C.byref(res)), "hpn_bam_sort_finish")
-        return res
+        return self._finish("hpn_bam_sort_finish", _lib.BamSortResult)
 
     def bam_sort_order(self, n):
         """order[j]: the input ordinal of the j-th record of the output."""
-        out = np.zeros(int(n), np.uint32)
-        self._ck(self.L.hpn_bam_sort_order(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_sort_order")
-        return out
+        return self._order("hpn_bam_sort_order", n)
 
     def bam_sort_sizes(self, n):
         """sizes[i]: 4 + block_size of input record i."""
@@ -851,9 +866,7 @@ class Context:
 
     def bam_sort_emit(self, first_record, max_records, last=False):
         """The next slice of the sorted records: gathered, cut, every closed block with its CRC-32 -> SplitInfo."""
-        info = _lib.SplitInfo()
-        self._ck(self.L.hpn_bam_sort_emit(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), "hpn_bam_sort_emit")
-        return info
+        return self._emit("hpn_bam_sort_emit", first_record, max_records, last)
 
     def bam_sort_blocks(self, n):
         """The n closed blocks of the last bam_sort_emit -> list of SplitBlock (off, len, crc, tid)."""
@@ -883,15 +896,11 @@ class Context:
 
     def bam_rmdup_add_raw_dev(self, d_raw):
         """The batch hpn_bam_raw_index_dev indexed last is classified and goes into the session's record store -> RmdupInfo."""
-        info = _lib.RmdupInfo()
-        self._ck(self.L.hpn_bam_rmdup_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), "hpn_bam_rmdup_add_raw_dev")
-        return info
+        return self._raw_add("hpn_bam_rmdup_add_raw_dev", _lib.RmdupInfo, d_raw)
 
     def bam_rmdup_finish(self):
         """Decides -> RmdupResult (n_records, n_out, payload_bytes, n_heads, the first record outside the domain)."""
-        res = _lib.RmdupResult()
-        self._ck(self.L.hpn_bam_rmdup_finish(self.h, C.byref(res)), "hpn_bam_rmdup_finish")
-        return res
+        return self._finish("hpn_bam_rmdup_finish", _lib.RmdupResult)
 
     def bam_rmdup_counts(self):
         """-> ([(checked, removed, first head's ordinal or -1)] per library, [(has records, unmatched names)] per target and, last,
@@ -903,15 +912,11 @@ class Context:
 
     def bam_rmdup_order(self, n):
         """order[j]: the input ordinal of the j-th record of the output."""
-        out = np.zeros(int(n), np.uint32)
-        self._ck(self.L.hpn_bam_rmdup_order(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_rmdup_order")
-        return out
+        return self._order("hpn_bam_rmdup_order", n)
 
     def bam_rmdup_emit(self, first_record, max_records, last=False):
         """The next slice of the surviving records: gathered, cut, every closed block with its CRC-32 -> SplitInfo."""
-        info = _lib.SplitInfo()
-        self._ck(self.L.hpn_bam_rmdup_emit(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), "hpn_bam_rmdup_emit")
-        return info
+        return self._emit("hpn_bam_rmdup_emit", first_record, max_records, last)
 
     def bam_rmdup_blocks(self, n):
         """The n closed blocks of the last bam_rmdup_emit -> list of SplitBlock (off, len, crc, tid)."""
@@ -939,27 +944,19 @@ class Context:
 
     def bam_merge_add_raw_dev(self, d_raw):
         """The batch hpn_bam_raw_index_dev indexed last goes into the session's record store (d_raw None: no records) -> BamMergeInfo."""
-        info = _lib.BamMergeInfo()
-        self._ck(self.L.hpn_bam_merge_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), "hpn_bam_merge_add_raw_dev")
-        return info
+        return self._raw_add("hpn_bam_merge_add_raw_dev", _lib.BamMergeInfo, d_raw)
 
     def bam_merge_finish(self):
         """Merges -> BamMergeResult (n_records, n_files, payload_bytes, n_lifted, the first record outside the domain, sort_bits)."""
-        res = _lib.BamMergeResult()
-        self._ck(self.L.hpn_bam_merge_finish(self.h, C.byref(res)), "hpn_bam_merge_finish")
-        return res
+        return self._finish("hpn_bam_merge_finish", _lib.BamMergeResult)
 
     def bam_merge_order(self, n):
         """order[j]: the session ordinal of the j-th record of the output."""
-        out = np.zeros(int(n), np.uint32)
-        self._ck(self.L.hpn_bam_merge_order(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_merge_order")
-        return out
+        return self._order("hpn_bam_merge_order", n)
 
     def bam_merge_emit(self, first_record, max_records, last=False):
         """The next slice of the merged records: gathered, cut, every closed block with its CRC-32 -> SplitInfo."""
-        info = _lib.SplitInfo()
-        self._ck(self.L.hpn_bam_merge_emit(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), "hpn_bam_merge_emit")
-        return info
+        return self._emit("hpn_bam_merge_emit", first_record, max_records, last)
 
     def bam_merge_blocks(self, n):
         """The n closed blocks of the last bam_merge_emit -> list of SplitBlock (off, len, crc, tid)."""
@@ -981,27 +978,19 @@ class Context:
 
     def bam_fixmate_add_raw_dev(self, d_raw):
         """The batch hpn_bam_raw_index_dev indexed last goes into the session's record store (d_raw None: no records) -> FixmateInfo."""
-        info = _lib.FixmateInfo()
-        self._ck(self.L.hpn_bam_fixmate_add_raw_dev(self.h, _ptr(d_raw) if d_raw is not None else None, C.byref(info)), "hpn_bam_fixmate_add_raw_dev")
-        return info
+        return self._raw_add("hpn_bam_fixmate_add_raw_dev", _lib.FixmateInfo, d_raw)
 
     def bam_fixmate_finish(self):
         """Decides -> FixmateResult (records in and out, pairs, singletons, CT fields, bytes added, the first record outside the domain)."""
-        res = _lib.FixmateResult()
-        self._ck(self.L.hpn_bam_fixmate_finish(self.h, C.byref(res)), "hpn_bam_fixmate_finish")
-        return res
+        return self._finish("hpn_bam_fixmate_finish", _lib.FixmateResult)
 
     def bam_fixmate_order(self, n):
         """order[j]: the session ordinal of the j-th record of the output."""
-        out = np.zeros(int(n), np.uint32)
-        self._ck(self.L.hpn_bam_fixmate_order(self.h, _ptr(out) if n else None, int(n)), "hpn_bam_fixmate_order")
-        return out
+        return self._order("hpn_bam_fixmate_order", n)
 
     def bam_fixmate_emit(self, first_record, max_records, last=False):
         """The next slice of the output: gathered, rewritten, cut, every closed block with its CRC-32 -> SplitInfo."""
-        info = _lib.SplitInfo()
-        self._ck(self.L.hpn_bam_fixmate_emit(self.h, int(first_record), int(max_records), 1 if last else 0, C.byref(info)), "hpn_bam_fixmate_emit")
-        return info
+        return self._emit("hpn_bam_fixmate_emit", first_record, max_records, last)
 
     def bam_fixmate_blocks(self, n):
         """The n closed blocks of the last bam_fixmate_emit -> list of SplitBlock (off, len, crc, tid)."""

@@ -1,5 +1,6 @@
-// bam_tool.hpp -- what the BAM tools over a device session do alike: the header read on the host (bam_sort, bam_rmdup), the
-// loop over the stream's batches (those two and bam_index), and the way from a session's slices to the BGZF writer (the two).
+// bam_tool.hpp -- what the BAM tools over a device session do alike: the header read on the host, the loop over the stream's
+// batches (bam_index too), and for the record-store sessions (bam_sort, bam_rmdup, bam_merge, bam_fixmate) the batches into the
+// session, its _finish, the way from its slices to the BGZF writer, and main()'s choice between the device and the host route.
 #pragma once
 #include "bam_gpu.hpp"
 #include "bam_sort_host.hpp"
@@ -49,8 +50,9 @@ static const uint64_t kSliceRecords = 1000;        // (the test-hooks build: the
 static const uint64_t kSliceRecords = 1u << 22;    // ~1 GB of payload per slice at 250 bytes a record
 #endif
 
-struct SliceCalls {        // a family's name (hpn_bam_sort, ...) and its _emit, _blocks, _payload_dev, _stored_dev
+struct SliceCalls {        // a family's name (hpn_bam_sort, ...), its tool's, and its _emit, _blocks, _payload_dev, _stored_dev
     std::string name;
+    const char *tool;
     int (*emit)(hpn_ctx *, uint64_t, uint64_t, int, hpn_split_info *);
     int (*blocks)(hpn_ctx *, uint64_t, hpn_split_block *, uint64_t, uint64_t *);
     int (*payload_dev)(hpn_ctx *, const uint8_t **, uint64_t *);
@@ -104,6 +106,105 @@ inline int write_slices(hpn_ctx *ctx, const SliceCalls &f, uint64_t n_out, int l
         first += cnt;
         if (last) return kSlicesDone;
     }
+}
+
+struct FeedRun {
+    double t_ingest = 0, t_store = 0;      // seconds waited for the batches, seconds in _add_raw_dev
+    uint64_t n_batches = 0;
+};
+
+// (with HPN_TIMING: why the device route ends here; r: a family's info or result)
+template <class R>
+inline void say_outside(const char *tool, bool timing, const R &r)
+{
+    if (timing)
+        fprintf(stderr, "[hpn] %s: record %lld (refID %d, pos %d) is outside the device's domain (reason %u)\n", tool, (long long)r.bad_record, r.bad_tid, r.bad_pos,
+                r.reason);
+}
+
+// Every batch of the stream into the session by the family's _add_raw_dev.  false: not for the device (each_batch's reasons, a
+// working set beyond the device's memory, a record outside the family's domain).
+template <class Info>
+inline bool feed_session(hpn_ctx *ctx, BgzfGpuStream &bam, const SliceCalls &f, int (*add)(hpn_ctx *, const uint8_t *, Info *), bool timing, FeedRun &run)
+{
+    return each_batch(bam, &run.t_ingest, [&](const BgzfDevice &) {
+        Info info;
+        const double t0 = wall_s();
+        const int rc = add(ctx, bam.d_raw(), &info);
+        if (rc == HPN_E_NOMEM) return false;               // the working set does not fit the device
+        if (rc != HPN_OK) die_hpn(ctx, rc, (f.name + "_add_raw_dev").c_str());
+        run.t_store += wall_s() - t0, ++run.n_batches;
+        if (info.bad_record < 0) return true;
+        say_outside(f.tool, timing, info);
+        return false;
+    });
+}
+
+// The family's _finish.  false: not for the device (its memory ran out, or a record only _finish can find lies outside the domain:
+// rmdup's and fixmate's do, and say so; sort's and merge's find none of their own, and a session feed_session saw die never comes
+// here, so for those two the line below cannot be reached and their messages are what they were).
+template <class Result>
+inline bool finish_session(hpn_ctx *ctx, const SliceCalls &f, int (*finish)(hpn_ctx *, Result *), bool timing, Result &res)
+{
+    const int rc = finish(ctx, &res);
+    if (rc == HPN_E_NOMEM) return false;
+    if (rc != HPN_OK) die_hpn(ctx, rc, (f.name + "_finish").c_str());
+    if (res.bad_record < 0) return true;
+    say_outside(f.tool, timing, res);
+    return false;
+}
+
+// The finished session's n_out records behind the header's plain blocks, to the writer's end.  create(head_blocks) is
+// write_slices' create().  kSlicesDone: `path` is written.  kSlicesNoOutput: create() said no.  kSlicesNoMem: not for the device,
+// and what was written is gone -- unless it went to stdout, where the device's memory running out behind the first slice is an
+// error (what has gone there cannot be taken back).  A write that fails ends the tool: "<says>: writing <path> failed", status 2.
+template <class Create>
+inline int write_session(hpn_ctx *ctx, const SliceCalls &f, const bamsort::Header &hdr, uint64_t n_out, int level, BgzfWriter &writer, const char *path,
+                         bool to_stdout, const char *says, Create &&create, SliceRun &run)
+{
+    const std::vector<uint8_t> head = hdr.bytes();
+    std::vector<uint8_t> head_blocks;
+    if (!bgzf_plain_blocks(head.data(), head.size(), level, head_blocks)) return kSlicesNoMem;
+    const int ws = write_slices(ctx, f, n_out, level, writer, to_stdout, [&]() { return create(head_blocks); }, run);
+    if (ws == kSlicesNoMem) {   // the output so far goes; the host route makes it again
+        if (run.created) writer.abandon();
+        if (run.created && !to_stdout) unlink(path);
+    }
+    if (ws != kSlicesDone) return ws;
+    if (!writer.finish()) {
+        fprintf(stderr, "%s: writing %s failed\n", says, path);
+        leave(2);
+    }
+    return kSlicesDone;
+}
+
+// main() of a tool with a device and a host route.  parse(): the arguments, not 0: main's status at once.  eligible(): the job is
+// the device's to try.  on_device(ctx, timing): 0 the output is written, 1 not for the device -- the host route starts over --,
+// 2 the job has ended with the reference's status 1.  on_host(): the host route's status.  HPN_TIMING says which route ran.
+template <class Parse, class Eligible, class Device, class Host>
+inline int run_tool(const char *tool, Parse &&parse, Eligible &&eligible, Device &&on_device, Host &&on_host)
+{
+    bind_before_runtime();
+    stamp("main");
+    const int early = parse();
+    if (early) return early;
+    const bool timing = getenv("HPN_TIMING") != nullptr;
+    if (eligible()) {
+        hpn_ctx *ctx = open_tool_ctx();
+        stamp("context created");
+        const int r = on_device(ctx, timing);
+        if (timing) fprintf(stderr, "[hpn] %s: %s\n", tool, r != 1 ? "device route" : "device route abandoned: host route");
+        if (r == 0) {
+            stamp("finished");
+            quick_exit_ok();
+        }
+        if (r == 2) leave(1);
+    } else if (timing) {
+        fprintf(stderr, "[hpn] %s: host route\n", tool);
+    }
+    const int status = on_host();
+    stamp("finished");
+    leave(status);
 }
 
 }  // namespace hpn

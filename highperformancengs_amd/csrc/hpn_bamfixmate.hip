@@ -17,34 +17,25 @@
 
 using namespace hpn;
 
-struct hpn_fixmate_work {   // what a new session must not inherit
-    BamStore st;
-    SliceOut out;
+struct hpn_fixmate_work : RecSession {   // what a new session must not inherit
     Scratch meta, cend, clen;                                                     // by ordinal, grown batch by batch
-    Scratch live, lidx, liveidx, head, rid, runstart, role, writes, woff, order;  // _finish
+    Scratch live, lidx, liveidx, head, rid, runstart, role, writes, woff, placed;  // _finish (placed: the output's order)
     Scratch pflag, pmtid, pmpos, pisize, extra, partner;
-    Scratch target_len, info;
-    bool open = false, dead = false, finished = false;
+    Scratch target_len;
     int remove_reads = 0;
     uint32_t n_targets = 0;
-    uint64_t n_out = 0;
-    BadRecord bad;
 };
 
 struct hpn_fixmate_state : FamilyState, hpn_fixmate_work {
     static constexpr int kSlot = kStBamFixmate;
+    static constexpr const char *kName = "hpn_bam_fixmate", *kVerb = "fixed";
+    static int wrong_count(hpn_ctx *c, const char *who, uint64_t n, uint64_t want)
+    {
+        return fail(c, HPN_E_ARG, "%s: %llu entries asked for, the output has %llu records", who, (unsigned long long)n, (unsigned long long)want);
+    }
 };
 
 namespace {
-
-hpn_fixmate_state *live(hpn_ctx *c, const char *who, bool want_finished)
-{
-    hpn_fixmate_state *u = state<hpn_fixmate_state>(c);
-    if (!u || !u->open) return fail(c, HPN_E_STATE, "%s before hpn_bam_fixmate_begin", who), nullptr;
-    if (want_finished && !u->finished) return fail(c, HPN_E_STATE, "%s before hpn_bam_fixmate_finish", who), nullptr;
-    if (want_finished && u->dead) return fail(c, HPN_E_STATE, "%s: a record lies outside the domain, nothing was fixed", who), nullptr;
-    return u;
-}
 
 FxRecords records_of(hpn_fixmate_state *u)
 {
@@ -93,63 +84,24 @@ int hpn_bam_fixmate_begin(hpn_ctx *c, int remove_reads, int32_t n_targets, const
 int hpn_bam_fixmate_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, hpn_fixmate_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_fixmate_state *u = live(c, "hpn_bam_fixmate_add_raw_dev", false);
+    hpn_fixmate_state *u = rec_live<hpn_fixmate_state>(c, "hpn_bam_fixmate_add_raw_dev", kRecFeeding);
     if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_fixmate_add_raw_dev behind hpn_bam_fixmate_finish");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    const uint64_t n = d_raw ? c->r_n : 0;
-    BamStore &st = u->st;
-    auto report = [&]() { info->n_records = n, info->store_bytes = st.len, bad_report(u->bad, info); };
-    report();
-    if (u->dead || !n) return HPN_OK;
-    if (st.records + n > kMaxRecords) {                // the first record the session cannot take
-        u->dead = true;
-        u->bad.record = (int64_t)kMaxRecords, u->bad.reason = kFxrRecords;
-        st.records += n;
-        report();
-        return HPN_OK;
-    }
-    int rc;
-    const uint64_t have = st.records, all = have + n;
-    if ((rc = grow_keep(c, u->meta, all * 4, have * 4)) != HPN_OK || (rc = grow_keep(c, u->cend, all * 4, have * 4)) != HPN_OK ||
-        (rc = grow_keep(c, u->clen, all * 4, have * 4)) != HPN_OK || (rc = bamstore_grow(c, st, n)) != HPN_OK)
-        return rc;
-    HPN_HIP(c, launch_bamfix_classify(d_raw, (const uint64_t *)c->r_off.p, n, have, st.len, u->n_targets, (const uint32_t *)u->target_len.p,
-                                      (uint32_t *)st.size.p, (u64 *)st.soff.p, (uint32_t *)u->meta.p, (int32_t *)u->cend.p, (uint32_t *)u->clen.p,
-                                      (u64 *)u->info.p, c->stream));
-    u64 h[3];
-    HPN_HIP(c, hipMemcpyAsync(h, u->info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (h[kBsBad] != ~0ull) {                          // the first record outside the domain: refID and pos for the message
-        if ((rc = bad_from_batch(c, d_raw, h[kBsBad] >> 3, have, (uint32_t)(h[kBsBad] & 7), u->bad)) != HPN_OK) return rc;
-        u->dead = true;
-        st.records = all;
-        report();
-        return HPN_OK;
-    }
-    if ((rc = bamstore_append(c, st, d_raw, h[kBsFirst], h[kBsEnd], n, "hpn_bam_fixmate")) != HPN_OK) return rc;
-    report();
-    return HPN_OK;
+    return rec_add(c, *u, d_raw, info, kFxrRecords, {{&u->meta, 4}, {&u->cend, 4}, {&u->clen, 4}}, [&](uint64_t n, uint64_t base) {
+        return launch_bamfix_classify(d_raw, (const uint64_t *)c->r_off.p, n, base, u->st.len, u->n_targets, (const uint32_t *)u->target_len.p,
+                                      (uint32_t *)u->st.size.p, (u64 *)u->st.soff.p, (uint32_t *)u->meta.p, (int32_t *)u->cend.p, (uint32_t *)u->clen.p,
+                                      (u64 *)u->info.p, c->stream);
+    }, rec_bad_of_batch<hpn_fixmate_state>);
 }
 
 int hpn_bam_fixmate_finish(hpn_ctx *c, hpn_fixmate_result *res)
 {
-    if (!c || !res) return HPN_E_ARG;
-    hpn_fixmate_state *u = live(c, "hpn_bam_fixmate_finish", false);
-    if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_fixmate_finish twice");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(res, 0, sizeof *res);
-    res->n_records = u->st.records;
-    bad_report(u->bad, res);
-    u->finished = true;
-    if (u->dead) return HPN_OK;
+    hpn_fixmate_state *u;
+    int rc = rec_finish_open(c, "hpn_bam_fixmate_finish", res, u);
+    if (!u) return rc;
     const uint64_t n = u->st.records;
-    int rc;
     if ((rc = sliceout_reserve(c, u->out, n)) != HPN_OK || (rc = need(c, u->live, n * 4)) != HPN_OK || (rc = need(c, u->lidx, (n + 1) * 4)) != HPN_OK ||
         (rc = need(c, u->role, n * 4)) != HPN_OK || (rc = need(c, u->writes, n * 4)) != HPN_OK || (rc = need(c, u->woff, (n + 1) * 4)) != HPN_OK ||
-        (rc = need(c, u->order, n * 4)) != HPN_OK || (rc = need(c, u->pflag, n * 4)) != HPN_OK || (rc = need(c, u->pmtid, n * 4)) != HPN_OK ||
+        (rc = need(c, u->placed, n * 4)) != HPN_OK || (rc = need(c, u->pflag, n * 4)) != HPN_OK || (rc = need(c, u->pmtid, n * 4)) != HPN_OK ||
         (rc = need(c, u->pmpos, n * 4)) != HPN_OK || (rc = need(c, u->pisize, n * 4)) != HPN_OK || (rc = need(c, u->extra, n * 4)) != HPN_OK ||
         (rc = need(c, u->partner, n * 4)) != HPN_OK)
         return rc;
@@ -176,7 +128,7 @@ int hpn_bam_fixmate_finish(hpn_ctx *c, hpn_fixmate_result *res)
     HPN_HIP(c, hipStreamSynchronize(c->stream));
     if ((rc = hpn_excl_scan(c, n ? u->writes.p : nullptr, 32, u->woff.p, 32, n)) != HPN_OK) return rc;
     HPN_HIP(c, launch_bamfix_plan(r, (const uint32_t *)u->lidx.p, (const uint32_t *)u->liveidx.p, n, (const uint32_t *)u->role.p,
-                                  (const uint32_t *)u->writes.p, (const uint32_t *)u->woff.p, (uint32_t *)u->order.p, patch_of(u), (u64 *)u->info.p, c->stream));
+                                  (const uint32_t *)u->writes.p, (const uint32_t *)u->woff.p, (uint32_t *)u->placed.p, patch_of(u), (u64 *)u->info.p, c->stream));
     u64 h[kBsWords];
     uint32_t triggered = 0, last_role = kFxSkipped, last_live = 0;
     HPN_HIP(c, hipMemcpyAsync(h, u->info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -188,9 +140,10 @@ int hpn_bam_fixmate_finish(hpn_ctx *c, hpn_fixmate_result *res)
         HPN_HIP(c, hipStreamSynchronize(c->stream));
     }
     u->n_out = (uint64_t)triggered + (last_role == kFxPending ? 1u : 0u);      // the pending record at the end of the file is written last
+    u->order = (const uint32_t *)u->placed.p;
     u->out.extra = (const uint32_t *)u->extra.p, u->out.grown = h[kFxAdded];
     u->out.patch = patch_slice, u->out.patch_arg = u;
-    if ((rc = sliceout_offsets(c, u->out, u->st, (const uint32_t *)u->order.p, u->n_out, !u->remove_reads, "hpn_bam_fixmate")) != HPN_OK) return rc;
+    if ((rc = sliceout_offsets(c, u->out, u->st, u->order, u->n_out, !u->remove_reads, "hpn_bam_fixmate")) != HPN_OK) return rc;
     res->n_out = u->n_out, res->n_pairs = h[kFxPairs], res->n_singletons = h[kFxSingles], res->n_tags = h[kFxTags], res->bytes_added = h[kFxAdded];
     res->payload_bytes = u->out.payload;
     return HPN_OK;
@@ -198,48 +151,27 @@ int hpn_bam_fixmate_finish(hpn_ctx *c, hpn_fixmate_result *res)
 
 int hpn_bam_fixmate_order(hpn_ctx *c, uint32_t *order, uint64_t n)
 {
-    if (!c || (n && !order)) return HPN_E_ARG;
-    hpn_fixmate_state *u = live(c, "hpn_bam_fixmate_order", true);
-    if (!u) return HPN_E_STATE;
-    if (n != u->n_out) return fail(c, HPN_E_ARG, "hpn_bam_fixmate_order: %llu entries asked for, the output has %llu records", (unsigned long long)n,
-                                   (unsigned long long)u->n_out);
-    if (!n) return HPN_OK;
-    HPN_HIP(c, hipSetDevice(c->device));
-    HPN_HIP(c, hipMemcpyAsync(order, u->order.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    return HPN_OK;
+    return rec_order<hpn_fixmate_state>(c, "hpn_bam_fixmate_order", order, n);
 }
 
 int hpn_bam_fixmate_emit(hpn_ctx *c, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info)
 {
-    if (!c || !info) return HPN_E_ARG;
-    hpn_fixmate_state *u = live(c, "hpn_bam_fixmate_emit", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_emit(c, u->out, u->st, (const uint32_t *)u->order.p, u->n_out, first_record, max_records, last, info, "hpn_bam_fixmate");
+    return rec_emit<hpn_fixmate_state>(c, "hpn_bam_fixmate_emit", first_record, max_records, last, info);
 }
 
 int hpn_bam_fixmate_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
 {
-    if (!c || !n) return HPN_E_ARG;
-    hpn_fixmate_state *u = live(c, "hpn_bam_fixmate_blocks", true);
-    if (!u) return HPN_E_STATE;
-    return list_blocks(c, u->out.list, first, out, cap, n);
+    return rec_blocks<hpn_fixmate_state>(c, "hpn_bam_fixmate_blocks", first, out, cap, n);
 }
 
 int hpn_bam_fixmate_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n_bytes)
 {
-    if (!c || !d_payload || !n_bytes) return HPN_E_ARG;
-    hpn_fixmate_state *u = live(c, "hpn_bam_fixmate_payload_dev", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_payload(u->out, d_payload, n_bytes);
+    return rec_payload<hpn_fixmate_state>(c, "hpn_bam_fixmate_payload_dev", d_payload, n_bytes);
 }
 
 int hpn_bam_fixmate_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_bytes)
 {
-    if (!c || !d_image || !n_bytes) return HPN_E_ARG;
-    hpn_fixmate_state *u = live(c, "hpn_bam_fixmate_stored_dev", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_stored(c, u->out, d_image, n_bytes);
+    return rec_stored<hpn_fixmate_state>(c, "hpn_bam_fixmate_stored_dev", d_image, n_bytes);
 }
 
 }  // extern "C"

@@ -18,32 +18,20 @@
 
 using namespace hpn;
 
-struct hpn_bammerge_work {   // what a new session must not inherit
-    BamStore st;
-    SliceOut out;
-    Scratch key, val, fid, tile_fid, tile_key, info;
-    bool open = false, dead = false, finished = false;
+struct hpn_bammerge_work : RecSession {   // what a new session must not inherit
+    Scratch key, val, fid, tile_fid, tile_key;
     uint64_t n_files = 0;
     uint32_t sort_bits = 0;
-    BadRecord bad;
 };
 
 struct hpn_bammerge_state : FamilyState, hpn_bammerge_work {
     static constexpr int kSlot = kStBamMerge;
+    static constexpr const char *kName = "hpn_bam_merge", *kVerb = "merged";
+    static int wrong_count(hpn_ctx *c, const char *who, uint64_t n, uint64_t want)
+    {
+        return fail(c, HPN_E_ARG, "%s: %llu entries asked for, the session holds %llu records", who, (unsigned long long)n, (unsigned long long)want);
+    }
 };
-
-namespace {
-
-hpn_bammerge_state *live(hpn_ctx *c, const char *who, bool want_finished)
-{
-    hpn_bammerge_state *u = state<hpn_bammerge_state>(c);
-    if (!u || !u->open) return fail(c, HPN_E_STATE, "%s before hpn_bam_merge_begin", who), nullptr;
-    if (want_finished && !u->finished) return fail(c, HPN_E_STATE, "%s before hpn_bam_merge_finish", who), nullptr;
-    if (want_finished && u->dead) return fail(c, HPN_E_STATE, "%s: a record lies outside the domain, nothing was merged", who), nullptr;
-    return u;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -66,9 +54,8 @@ int hpn_bam_merge_begin(hpn_ctx *c)
 int hpn_bam_merge_next_file(hpn_ctx *c)
 {
     if (!c) return HPN_E_ARG;
-    hpn_bammerge_state *u = live(c, "hpn_bam_merge_next_file", false);
+    hpn_bammerge_state *u = rec_live<hpn_bammerge_state>(c, "hpn_bam_merge_next_file", kRecFeeding);
     if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_merge_next_file behind hpn_bam_merge_finish");
     if (u->n_files >= 0xffffffffull) return fail(c, HPN_E_ARG, "hpn_bam_merge_next_file: more than 2^32 - 1 files");
     ++u->n_files;
     return HPN_OK;
@@ -77,60 +64,23 @@ int hpn_bam_merge_next_file(hpn_ctx *c)
 int hpn_bam_merge_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, hpn_bammerge_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_bammerge_state *u = live(c, "hpn_bam_merge_add_raw_dev", false);
+    hpn_bammerge_state *u = rec_live<hpn_bammerge_state>(c, "hpn_bam_merge_add_raw_dev", kRecFeeding);
     if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_merge_add_raw_dev behind hpn_bam_merge_finish");
     if (!u->n_files) return fail(c, HPN_E_STATE, "hpn_bam_merge_add_raw_dev before the first hpn_bam_merge_next_file");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    const uint64_t n = d_raw ? c->r_n : 0;
-    BamStore &st = u->st;
-    auto report = [&]() { info->n_records = n, info->store_bytes = st.len, bad_report(u->bad, info); };
-    report();
-    if (u->dead || !n) return HPN_OK;
-    if (st.records + n > kMaxRecords) {                // the first record the sort cannot take
-        u->dead = true;
-        u->bad.record = (int64_t)kMaxRecords, u->bad.reason = 2;
-        st.records += n;
-        report();
-        return HPN_OK;
-    }
-    int rc;
-    const uint64_t have = st.records, all = have + n;
-    if ((rc = grow_keep(c, u->key, all * 8, have * 8)) != HPN_OK || (rc = grow_keep(c, u->val, all * 4, have * 4)) != HPN_OK ||
-        (rc = grow_keep(c, u->fid, all * 4, have * 4)) != HPN_OK || (rc = bamstore_grow(c, st, n)) != HPN_OK)
-        return rc;
-    HPN_HIP(c, launch_bammerge_keys(d_raw, (const uint64_t *)c->r_off.p, n, have, st.len, (uint32_t)(u->n_files - 1), (u64 *)u->key.p, (uint32_t *)u->val.p,
-                                    (uint32_t *)u->fid.p, (uint32_t *)st.size.p, (u64 *)st.soff.p, (u64 *)u->info.p, c->stream));
-    u64 h[3];
-    HPN_HIP(c, hipMemcpyAsync(h, u->info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (h[kBsBad] != ~0ull) {                          // the first record with the HEAP_EMPTY key: refID and pos for the message
-        if ((rc = bad_from_batch(c, d_raw, h[kBsBad] >> 3, have, (uint32_t)(h[kBsBad] & 7), u->bad)) != HPN_OK) return rc;
-        u->dead = true;
-        st.records = all;
-        report();
-        return HPN_OK;
-    }
-    if ((rc = bamstore_append(c, st, d_raw, h[kBsFirst], h[kBsEnd], n, "hpn_bam_merge")) != HPN_OK) return rc;
-    report();
-    return HPN_OK;
+    // (a bad record here is the first one with the HEAP_EMPTY key)
+    return rec_add(c, *u, d_raw, info, kBmrRecords, {{&u->key, 8}, {&u->val, 4}, {&u->fid, 4}}, [&](uint64_t n, uint64_t base) {
+        return launch_bammerge_keys(d_raw, (const uint64_t *)c->r_off.p, n, base, u->st.len, (uint32_t)(u->n_files - 1), (u64 *)u->key.p, (uint32_t *)u->val.p,
+                                    (uint32_t *)u->fid.p, (uint32_t *)u->st.size.p, (u64 *)u->st.soff.p, (u64 *)u->info.p, c->stream);
+    }, rec_bad_of_batch<hpn_bammerge_state>);
 }
 
 int hpn_bam_merge_finish(hpn_ctx *c, hpn_bammerge_result *res)
 {
-    if (!c || !res) return HPN_E_ARG;
-    hpn_bammerge_state *u = live(c, "hpn_bam_merge_finish", false);
-    if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_merge_finish twice");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(res, 0, sizeof *res);
-    res->n_records = u->st.records, res->n_files = u->n_files;
-    bad_report(u->bad, res);
-    u->finished = true;
-    if (u->dead) return HPN_OK;
+    hpn_bammerge_state *u;
+    int rc = rec_finish_open(c, "hpn_bam_merge_finish", res, u, [](hpn_bammerge_state &s, hpn_bammerge_result *r) { r->n_files = s.n_files; });
+    if (!u) return rc;
     const uint64_t n = u->st.records, tiles = bammerge_tiles(n);
-    int rc;
+    u->order = (const uint32_t *)u->val.p, u->n_out = n;         // (val: the ordinals, sorted in place below)
     if ((rc = sliceout_reserve(c, u->out, n)) != HPN_OK || (rc = need(c, u->tile_fid, (tiles + 1) * 4)) != HPN_OK ||
         (rc = need(c, u->tile_key, (tiles + 1) * 8)) != HPN_OK)
         return rc;
@@ -145,55 +95,34 @@ int hpn_bam_merge_finish(hpn_ctx *c, hpn_bammerge_result *res)
     if (n > 1 && u->sort_bits &&
         (rc = hpn_sort_pairs_u64_bits(c, (uint64_t *)u->key.p, (uint32_t *)u->val.p, n, 0, (int)u->sort_bits)) != HPN_OK)
         return rc;
-    if ((rc = sliceout_offsets(c, u->out, u->st, (const uint32_t *)u->val.p, n, true, "hpn_bam_merge")) != HPN_OK) return rc;
+    if ((rc = sliceout_offsets(c, u->out, u->st, u->order, n, true, "hpn_bam_merge")) != HPN_OK) return rc;
     res->payload_bytes = u->out.payload, res->n_lifted = h[kBmLifted], res->sort_bits = u->sort_bits;
     return HPN_OK;
 }
 
 int hpn_bam_merge_order(hpn_ctx *c, uint32_t *order, uint64_t n)
 {
-    if (!c || (n && !order)) return HPN_E_ARG;
-    hpn_bammerge_state *u = live(c, "hpn_bam_merge_order", true);
-    if (!u) return HPN_E_STATE;
-    if (n != u->st.records) return fail(c, HPN_E_ARG, "hpn_bam_merge_order: %llu entries asked for, the session holds %llu records", (unsigned long long)n,
-                                     (unsigned long long)u->st.records);
-    if (!n) return HPN_OK;
-    HPN_HIP(c, hipSetDevice(c->device));
-    HPN_HIP(c, hipMemcpyAsync(order, u->val.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    return HPN_OK;
+    return rec_order<hpn_bammerge_state>(c, "hpn_bam_merge_order", order, n);
 }
 
 int hpn_bam_merge_emit(hpn_ctx *c, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info)
 {
-    if (!c || !info) return HPN_E_ARG;
-    hpn_bammerge_state *u = live(c, "hpn_bam_merge_emit", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_emit(c, u->out, u->st, (const uint32_t *)u->val.p, u->st.records, first_record, max_records, last, info, "hpn_bam_merge");
+    return rec_emit<hpn_bammerge_state>(c, "hpn_bam_merge_emit", first_record, max_records, last, info);
 }
 
 int hpn_bam_merge_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
 {
-    if (!c || !n) return HPN_E_ARG;
-    hpn_bammerge_state *u = live(c, "hpn_bam_merge_blocks", true);
-    if (!u) return HPN_E_STATE;
-    return list_blocks(c, u->out.list, first, out, cap, n);
+    return rec_blocks<hpn_bammerge_state>(c, "hpn_bam_merge_blocks", first, out, cap, n);
 }
 
 int hpn_bam_merge_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n_bytes)
 {
-    if (!c || !d_payload || !n_bytes) return HPN_E_ARG;
-    hpn_bammerge_state *u = live(c, "hpn_bam_merge_payload_dev", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_payload(u->out, d_payload, n_bytes);
+    return rec_payload<hpn_bammerge_state>(c, "hpn_bam_merge_payload_dev", d_payload, n_bytes);
 }
 
 int hpn_bam_merge_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_bytes)
 {
-    if (!c || !d_image || !n_bytes) return HPN_E_ARG;
-    hpn_bammerge_state *u = live(c, "hpn_bam_merge_stored_dev", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_stored(c, u->out, d_image, n_bytes);
+    return rec_stored<hpn_bammerge_state>(c, "hpn_bam_merge_stored_dev", d_image, n_bytes);
 }
 
 }  // extern "C"

@@ -1,16 +1,22 @@
 // hpn_bamrec.hpp -- what the BAM sessions keep and do alike, next to the cuts themselves (hpn_cuts.hpp):
-//   BadRecord   the first record outside a family's domain, fetched and reported in one place (split, bai, sort, rmdup);
-//   BamStore    the records of every batch behind one another on the device, with each one's size and place (sort, rmdup);
+//   BadRecord   the first record outside a family's domain, fetched and reported in one place (split, bai and the four below);
+//   BamStore    the records of every batch behind one another on the device, with each one's size and place;
 //   SliceOut    the stored records in the order a family decided, handed back slice by slice: gathered behind the block the
-//               slice before left open, cut as bam_write1 would, CRC-32, for level 0 the stored image (sort, rmdup).  A family
-//               whose output records are not the stored ones byte for byte (fixmate) gives `extra` -- output record j takes
+//               slice before left open, cut as bam_write1 would, CRC-32, for level 0 the stored image.  A family whose output
+//               records are not the stored ones byte for byte (fixmate) gives `extra` -- output record j takes
 //               size[order[j]] + extra[order[j]] bytes -- and `patch`, which runs on the gathered slice in front of the cuts and
-//               the CRC-32; without the two the slices are what they were.
-// A family writes its per-record kernel (size[], soff[] and info words [0..2] as k_sort_keys fills them), its _finish and its
-// order array.  Plain movable values: a session resets by assigning fresh ones.
+//               the CRC-32; without the two the slices are what they were;
+//   RecSession  the three and the life cycle around them (sort, rmdup, merge, fixmate): _begin, batches until _finish, then the
+//               output's slices; a record outside the domain kills the session and every later call says so.  rec_live is the one
+//               check of that cycle, rec_add the batch around a family's kernel, rec_finish_open the head of _finish, and
+//               rec_order / rec_emit / rec_blocks / rec_payload / rec_stored the bodies behind a finished session's calls.
+// A family writes its _begin, its per-record kernel (size[], soff[] and info words [0..2], see kInfoBad), the middle of its
+// _finish, which sets `order` and `n_out`, and every extern "C" function under its own name as a forward.  Plain movable values:
+// a session resets by assigning fresh ones.
 #pragma once
 #include <string.h>
 
+#include <initializer_list>
 #include <vector>
 
 #include "hpn_cuts.hpp"
@@ -45,7 +51,8 @@ inline int bad_from_batch(hpn_ctx *c, const uint8_t *d_raw, uint64_t ord, uint64
     return HPN_OK;
 }
 
-constexpr uint64_t kMaxRecords = (1ull << 31) - 1;     // a store's contract; the reason a family reports at the cap is its own
+constexpr uint64_t kMaxRecords = (1ull << 31) - 1;     // a store's contract; the reason a family reports at the cap is its own:
+enum { kBsrRecords = 3, kBmrRecords = 2 };             // sort's and merge's (include/hpngs.h; rmdup's kRsRecords, fixmate's kFxrRecords)
 
 struct BamStore {
     Scratch store, size, soff;       // the records' bytes; by ordinal: 4 + block_size, where the record lies in `store`
@@ -191,6 +198,171 @@ inline int sliceout_stored(hpn_ctx *c, SliceOut &o, const uint8_t **d_image, uin
     }
     *d_image = (const uint8_t *)o.cw.img.p, *n_bytes = o.stored_bytes;
     return HPN_OK;
+}
+
+// ---- the session around the three ----
+// Words 0, 1, 2 of every family's info array, whatever else it keeps there: the lowest (ordinal << bits | reason) of a record outside
+// the domain (~0: none), and where in the inflated stream the batch's first record starts and its last one ends.
+enum { kInfoBad = 0, kInfoFirst = 1, kInfoEnd = 2, kInfoHead = 3 };
+static_assert(kBsBad == kInfoBad && kBsFirst == kInfoFirst && kBsEnd == kInfoEnd, "k_sort_keys' info words are the sessions'");
+
+struct RecSession {        // what a new session must not inherit: _begin assigns a fresh one
+    BamStore st;
+    SliceOut out;
+    Scratch info;
+    bool open = false, dead = false, finished = false;
+    BadRecord bad;
+    const uint32_t *order = nullptr;     // the output: record j is stored record order[j], j < n_out (the family's _finish sets both)
+    uint64_t n_out = 0;
+};
+
+// A state type U derives from FamilyState and RecSession and names itself: kName ("hpn_bam_sort"), kVerb (what _finish does to
+// the records: "sorted") and wrong_count(c, who, n, want), the refusal of n entries asked for where the session has `want`.
+enum RecWant { kRecFeeding, kRecFinishing, kRecFinished };       // a call in front of _finish, _finish itself, a call behind it
+
+template <class U>
+inline U *rec_live(hpn_ctx *c, const char *who, RecWant want)
+{
+    U *u = state<U>(c);
+    if (!u || !u->open) return fail(c, HPN_E_STATE, "%s before %s_begin", who, U::kName), nullptr;
+    if (want == kRecFinished) {
+        if (!u->finished) return fail(c, HPN_E_STATE, "%s before %s_finish", who, U::kName), nullptr;
+        if (u->dead) return fail(c, HPN_E_STATE, "%s: a record lies outside the domain, nothing was %s", who, U::kVerb), nullptr;
+    } else if (u->finished) {
+        if (want == kRecFinishing) return fail(c, HPN_E_STATE, "%s twice", who), nullptr;
+        return fail(c, HPN_E_STATE, "%s behind %s_finish", who, U::kName), nullptr;
+    }
+    return u;
+}
+
+struct ByOrdinal {         // an array a family keeps by ordinal and grows batch by batch, and its entry's bytes
+    Scratch *s;
+    uint32_t width;
+};
+
+// how most kernels pack word kInfoBad: 3 reason bits; refID and pos from the batch
+template <class U>
+inline int rec_bad_of_batch(hpn_ctx *c, U &u, const uint8_t *d_raw, u64 word, uint64_t base)
+{
+    return bad_from_batch(c, d_raw, word >> 3, base, (uint32_t)(word & 7), u.bad);
+}
+
+// One indexed batch (hpn_bam_raw_index_dev's last) into a live session: arrays[] and the store's grown, launch(n, base) -- the
+// family's kernel over the batch's n records, ordinals base.. --, then the records appended, or the session killed by the first
+// record outside the domain, which bad_of(c, u, d_raw, word, base) makes of word kInfoBad, or by the cap, with cap_reason.
+template <class U, class Info, class Launch, class BadOf>
+inline int rec_add(hpn_ctx *c, U &u, const uint8_t *d_raw, Info *info, uint32_t cap_reason, std::initializer_list<ByOrdinal> arrays, Launch &&launch,
+                   BadOf &&bad_of)
+{
+    HPN_HIP(c, hipSetDevice(c->device));
+    memset(info, 0, sizeof *info);
+    const uint64_t n = d_raw ? c->r_n : 0;
+    BamStore &st = u.st;
+    auto report = [&]() { info->n_records = n, info->store_bytes = st.len, bad_report(u.bad, info); };
+    report();
+    if (u.dead || !n) return HPN_OK;
+    if (st.records + n > kMaxRecords) {                // the first record the session cannot take
+        u.dead = true;
+        u.bad.record = (int64_t)kMaxRecords, u.bad.reason = cap_reason;
+        st.records += n;
+        report();
+        return HPN_OK;
+    }
+    int rc;
+    const uint64_t have = st.records, all = have + n;
+    for (const ByOrdinal &a : arrays)
+        if ((rc = grow_keep(c, *a.s, all * a.width, have * a.width)) != HPN_OK) return rc;
+    if ((rc = bamstore_grow(c, st, n)) != HPN_OK) return rc;
+    HPN_HIP(c, launch(n, have));
+    u64 h[kInfoHead];
+    HPN_HIP(c, hipMemcpyAsync(h, u.info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HPN_HIP(c, hipStreamSynchronize(c->stream));
+    if (h[kInfoBad] != ~0ull) {                        // the first record outside the domain: refID and pos for the message
+        if ((rc = bad_of(c, u, d_raw, h[kInfoBad], have)) != HPN_OK) return rc;
+        u.dead = true;
+        st.records = all;
+        report();
+        return HPN_OK;
+    }
+    if ((rc = bamstore_append(c, st, d_raw, h[kInfoFirst], h[kInfoEnd], n, U::kName)) != HPN_OK) return rc;
+    report();
+    return HPN_OK;
+}
+
+// The head of _finish.  u == nullptr behind it: return what it returned -- a refusal, or HPN_OK for a session a record has killed,
+// which *res says.  more(u, res): what the family's result holds beside n_records and the bad record, whether the session lives or not.
+template <class U, class Res, class More>
+inline int rec_finish_open(hpn_ctx *c, const char *who, Res *res, U *&u, More &&more)
+{
+    u = nullptr;
+    if (!c || !res) return HPN_E_ARG;
+    U *s = rec_live<U>(c, who, kRecFinishing);
+    if (!s) return HPN_E_STATE;
+    HPN_HIP(c, hipSetDevice(c->device));
+    memset(res, 0, sizeof *res);
+    res->n_records = s->st.records;
+    bad_report(s->bad, res);
+    more(*s, res);
+    s->finished = true;
+    if (!s->dead) u = s;
+    return HPN_OK;
+}
+
+template <class U, class Res>
+inline int rec_finish_open(hpn_ctx *c, const char *who, Res *res, U *&u)
+{
+    return rec_finish_open(c, who, res, u, [](U &, Res *) {});
+}
+
+// src[0..n) of a finished session to the host (the caller has held n to what the session has: U::wrong_count says the refusal)
+inline int rec_copy_out(hpn_ctx *c, uint32_t *dst, const void *src, uint64_t n)
+{
+    if (!n) return HPN_OK;
+    HPN_HIP(c, hipSetDevice(c->device));
+    HPN_HIP(c, hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HPN_HIP(c, hipStreamSynchronize(c->stream));
+    return HPN_OK;
+}
+
+template <class U>
+inline int rec_order(hpn_ctx *c, const char *who, uint32_t *order, uint64_t n)
+{
+    if (!c || (n && !order)) return HPN_E_ARG;
+    U *u = rec_live<U>(c, who, kRecFinished);
+    if (!u) return HPN_E_STATE;
+    return n != u->n_out ? U::wrong_count(c, who, n, u->n_out) : rec_copy_out(c, order, u->order, n);
+}
+
+template <class U>
+inline int rec_emit(hpn_ctx *c, const char *who, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info)
+{
+    if (!c || !info) return HPN_E_ARG;
+    U *u = rec_live<U>(c, who, kRecFinished);
+    return !u ? HPN_E_STATE : sliceout_emit(c, u->out, u->st, u->order, u->n_out, first_record, max_records, last, info, U::kName);
+}
+
+template <class U>
+inline int rec_blocks(hpn_ctx *c, const char *who, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
+{
+    if (!c || !n) return HPN_E_ARG;
+    U *u = rec_live<U>(c, who, kRecFinished);
+    return !u ? HPN_E_STATE : list_blocks(c, u->out.list, first, out, cap, n);
+}
+
+template <class U>
+inline int rec_payload(hpn_ctx *c, const char *who, const uint8_t **d_payload, uint64_t *n_bytes)
+{
+    if (!c || !d_payload || !n_bytes) return HPN_E_ARG;
+    U *u = rec_live<U>(c, who, kRecFinished);
+    return !u ? HPN_E_STATE : sliceout_payload(u->out, d_payload, n_bytes);
+}
+
+template <class U>
+inline int rec_stored(hpn_ctx *c, const char *who, const uint8_t **d_image, uint64_t *n_bytes)
+{
+    if (!c || !d_image || !n_bytes) return HPN_E_ARG;
+    U *u = rec_live<U>(c, who, kRecFinished);
+    return !u ? HPN_E_STATE : sliceout_stored(c, u->out, d_image, n_bytes);
 }
 
 }  // namespace hpn

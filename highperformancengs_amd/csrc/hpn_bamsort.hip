@@ -16,32 +16,20 @@
 
 using namespace hpn;
 
-struct hpn_bamsort_work {   // what a new session must not inherit
-    BamStore st;
-    SliceOut out;
-    Scratch key, val, info;
-    bool open = false, dead = false, finished = false;
+struct hpn_bamsort_work : RecSession {   // what a new session must not inherit
+    Scratch key, val;
     uint32_t sort_bits = 0;
-    BadRecord bad;
     uint64_t fresh_mem = 0;
 };
 
 struct hpn_bamsort_state : FamilyState, hpn_bamsort_work {
     static constexpr int kSlot = kStBamSort;
+    static constexpr const char *kName = "hpn_bam_sort", *kVerb = "sorted";
+    static int wrong_count(hpn_ctx *c, const char *who, uint64_t n, uint64_t want)
+    {
+        return fail(c, HPN_E_ARG, "%s: %llu entries asked for, the session holds %llu records", who, (unsigned long long)n, (unsigned long long)want);
+    }
 };
-
-namespace {
-
-hpn_bamsort_state *live(hpn_ctx *c, const char *who, bool want_finished)
-{
-    hpn_bamsort_state *u = state<hpn_bamsort_state>(c);
-    if (!u || !u->open) return fail(c, HPN_E_STATE, "%s before hpn_bam_sort_begin", who), nullptr;
-    if (want_finished && !u->finished) return fail(c, HPN_E_STATE, "%s before hpn_bam_sort_finish", who), nullptr;
-    if (want_finished && u->dead) return fail(c, HPN_E_STATE, "%s: a record lies outside the domain, nothing was sorted", who), nullptr;
-    return u;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -64,59 +52,21 @@ int hpn_bam_sort_begin(hpn_ctx *c)
 int hpn_bam_sort_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, hpn_bamsort_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_bamsort_state *u = live(c, "hpn_bam_sort_add_raw_dev", false);
+    hpn_bamsort_state *u = rec_live<hpn_bamsort_state>(c, "hpn_bam_sort_add_raw_dev", kRecFeeding);
     if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_sort_add_raw_dev behind hpn_bam_sort_finish");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    const uint64_t n = d_raw ? c->r_n : 0;
-    BamStore &st = u->st;
-    auto report = [&]() { info->n_records = n, info->store_bytes = st.len, bad_report(u->bad, info); };
-    report();
-    if (u->dead || !n) return HPN_OK;
-    if (st.records + n > kMaxRecords) {                // the first record the sort cannot take
-        u->dead = true;
-        u->bad.record = (int64_t)kMaxRecords, u->bad.reason = 3;
-        st.records += n;
-        report();
-        return HPN_OK;
-    }
-    int rc;
-    const uint64_t have = st.records, all = have + n;
-    if ((rc = grow_keep(c, u->key, all * 8, have * 8)) != HPN_OK || (rc = grow_keep(c, u->val, all * 4, have * 4)) != HPN_OK ||
-        (rc = bamstore_grow(c, st, n)) != HPN_OK)
-        return rc;
-    HPN_HIP(c, launch_bamsort_keys(d_raw, (const uint64_t *)c->r_off.p, n, have, st.len, (u64 *)u->key.p, (uint32_t *)u->val.p, (uint32_t *)st.size.p,
-                                   (u64 *)st.soff.p, (u64 *)u->info.p, c->stream));
-    u64 h[3];
-    HPN_HIP(c, hipMemcpyAsync(h, u->info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (h[kBsBad] != ~0ull) {                          // the first record outside the domain: refID and pos for the message
-        if ((rc = bad_from_batch(c, d_raw, h[kBsBad] >> 3, have, (uint32_t)(h[kBsBad] & 7), u->bad)) != HPN_OK) return rc;
-        u->dead = true;
-        st.records = all;
-        report();
-        return HPN_OK;
-    }
-    if ((rc = bamstore_append(c, st, d_raw, h[kBsFirst], h[kBsEnd], n, "hpn_bam_sort")) != HPN_OK) return rc;
-    report();
-    return HPN_OK;
+    return rec_add(c, *u, d_raw, info, kBsrRecords, {{&u->key, 8}, {&u->val, 4}}, [&](uint64_t n, uint64_t base) {
+        return launch_bamsort_keys(d_raw, (const uint64_t *)c->r_off.p, n, base, u->st.len, (u64 *)u->key.p, (uint32_t *)u->val.p, (uint32_t *)u->st.size.p,
+                                   (u64 *)u->st.soff.p, (u64 *)u->info.p, c->stream);
+    }, rec_bad_of_batch<hpn_bamsort_state>);
 }
 
 int hpn_bam_sort_finish(hpn_ctx *c, hpn_bamsort_result *res)
 {
-    if (!c || !res) return HPN_E_ARG;
-    hpn_bamsort_state *u = live(c, "hpn_bam_sort_finish", false);
-    if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_sort_finish twice");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(res, 0, sizeof *res);
-    res->n_records = u->st.records;
-    bad_report(u->bad, res);
-    u->finished = true;
-    if (u->dead) return HPN_OK;
+    hpn_bamsort_state *u;
+    int rc = rec_finish_open(c, "hpn_bam_sort_finish", res, u);
+    if (!u) return rc;
     const uint64_t n = u->st.records;
-    int rc;
+    u->order = (const uint32_t *)u->val.p, u->n_out = n;         // (val: the ordinals, sorted in place below)
     if ((rc = sliceout_reserve(c, u->out, n)) != HPN_OK) return rc;
     HPN_HIP(c, launch_bamsort_rank((u64 *)u->key.p, n, (u64 *)u->info.p, c->stream));
     u64 h[kBsWords];
@@ -127,69 +77,42 @@ int hpn_bam_sort_finish(hpn_ctx *c, hpn_bamsort_result *res)
     if (n > 1 && u->sort_bits &&
         (rc = hpn_sort_pairs_u64_bits(c, (uint64_t *)u->key.p, (uint32_t *)u->val.p, n, 0, (int)u->sort_bits)) != HPN_OK)
         return rc;
-    if ((rc = sliceout_offsets(c, u->out, u->st, (const uint32_t *)u->val.p, n, true, "hpn_bam_sort")) != HPN_OK) return rc;
+    if ((rc = sliceout_offsets(c, u->out, u->st, u->order, n, true, "hpn_bam_sort")) != HPN_OK) return rc;
     res->payload_bytes = u->out.payload, res->fresh_mem = u->fresh_mem, res->sort_bits = u->sort_bits;
     return HPN_OK;
 }
 
 int hpn_bam_sort_order(hpn_ctx *c, uint32_t *order, uint64_t n)
 {
-    if (!c || (n && !order)) return HPN_E_ARG;
-    hpn_bamsort_state *u = live(c, "hpn_bam_sort_order", true);
-    if (!u) return HPN_E_STATE;
-    if (n != u->st.records) return fail(c, HPN_E_ARG, "hpn_bam_sort_order: %llu entries asked for, the session holds %llu records", (unsigned long long)n,
-                                     (unsigned long long)u->st.records);
-    if (!n) return HPN_OK;
-    HPN_HIP(c, hipSetDevice(c->device));
-    HPN_HIP(c, hipMemcpyAsync(order, u->val.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    return HPN_OK;
+    return rec_order<hpn_bamsort_state>(c, "hpn_bam_sort_order", order, n);
 }
 
 int hpn_bam_sort_sizes(hpn_ctx *c, uint32_t *sizes, uint64_t n)
 {
     if (!c || (n && !sizes)) return HPN_E_ARG;
-    hpn_bamsort_state *u = live(c, "hpn_bam_sort_sizes", true);
+    hpn_bamsort_state *u = rec_live<hpn_bamsort_state>(c, "hpn_bam_sort_sizes", kRecFinished);
     if (!u) return HPN_E_STATE;
-    if (n != u->st.records) return fail(c, HPN_E_ARG, "hpn_bam_sort_sizes: %llu entries asked for, the session holds %llu records", (unsigned long long)n,
-                                     (unsigned long long)u->st.records);
-    if (!n) return HPN_OK;
-    HPN_HIP(c, hipSetDevice(c->device));
-    HPN_HIP(c, hipMemcpyAsync(sizes, u->st.size.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    return HPN_OK;
+    return n != u->st.records ? u->wrong_count(c, "hpn_bam_sort_sizes", n, u->st.records) : rec_copy_out(c, sizes, u->st.size.p, n);
 }
 
 int hpn_bam_sort_emit(hpn_ctx *c, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info)
 {
-    if (!c || !info) return HPN_E_ARG;
-    hpn_bamsort_state *u = live(c, "hpn_bam_sort_emit", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_emit(c, u->out, u->st, (const uint32_t *)u->val.p, u->st.records, first_record, max_records, last, info, "hpn_bam_sort");
+    return rec_emit<hpn_bamsort_state>(c, "hpn_bam_sort_emit", first_record, max_records, last, info);
 }
 
 int hpn_bam_sort_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
 {
-    if (!c || !n) return HPN_E_ARG;
-    hpn_bamsort_state *u = live(c, "hpn_bam_sort_blocks", true);
-    if (!u) return HPN_E_STATE;
-    return list_blocks(c, u->out.list, first, out, cap, n);
+    return rec_blocks<hpn_bamsort_state>(c, "hpn_bam_sort_blocks", first, out, cap, n);
 }
 
 int hpn_bam_sort_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n_bytes)
 {
-    if (!c || !d_payload || !n_bytes) return HPN_E_ARG;
-    hpn_bamsort_state *u = live(c, "hpn_bam_sort_payload_dev", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_payload(u->out, d_payload, n_bytes);
+    return rec_payload<hpn_bamsort_state>(c, "hpn_bam_sort_payload_dev", d_payload, n_bytes);
 }
 
 int hpn_bam_sort_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_bytes)
 {
-    if (!c || !d_image || !n_bytes) return HPN_E_ARG;
-    hpn_bamsort_state *u = live(c, "hpn_bam_sort_stored_dev", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_stored(c, u->out, d_image, n_bytes);
+    return rec_stored<hpn_bamsort_state>(c, "hpn_bam_sort_stored_dev", d_image, n_bytes);
 }
 
 }  // extern "C"

@@ -21,33 +21,27 @@ namespace {
 constexpr uint32_t kMaxIds = 1u << 16;
 }  // namespace
 
-struct hpn_rmdup_work {   // what a new session must not inherit
-    BamStore st;
-    SliceOut out;
+struct hpn_rmdup_work : RecSession {   // what a new session must not inherit
     Scratch tp, cls, isize, qsum, lib, hash;                                                     // by ordinal, grown batch by batch
     Scratch rb, hf, rsc, hsc, rid, runstart, evkind, evrec, slot, drop, now, sl, cnow, cslot;    // _finish
-    Scratch hkey, hval, ekey, eval, order;
-    Scratch id_bytes, id_off, id_lib, libs, unmatched, present, info;
-    bool open = false, dead = false, finished = false;
+    Scratch hkey, hval, ekey, eval, placed;                                                      // (placed: the output's order)
+    Scratch id_bytes, id_off, id_lib, libs, unmatched, present;
     uint32_t n_ref = 0, n_ids = 0, n_libs = 0;
-    uint64_t n_out = 0, n_heads = 0;
-    BadRecord bad;
+    uint64_t n_heads = 0;
 };
 
 struct hpn_rmdup_state : FamilyState, hpn_rmdup_work {
     static constexpr int kSlot = kStBamRmdup;
+    static constexpr const char *kName = "hpn_bam_rmdup", *kVerb = "decided";
+    static int wrong_count(hpn_ctx *c, const char *who, uint64_t n, uint64_t want)
+    {
+        return fail(c, HPN_E_ARG, "%s: %llu entries asked for, %llu records survive", who, (unsigned long long)n, (unsigned long long)want);
+    }
 };
 
-namespace {
+static_assert(kRmBad == kInfoBad && kRmFirst == kInfoFirst && kRmEnd == kInfoEnd, "k_rm_classify's info words are the sessions'");
 
-hpn_rmdup_state *live(hpn_ctx *c, const char *who, bool want_finished)
-{
-    hpn_rmdup_state *u = state<hpn_rmdup_state>(c);
-    if (!u || !u->open) return fail(c, HPN_E_STATE, "%s before hpn_bam_rmdup_begin", who), nullptr;
-    if (want_finished && !u->finished) return fail(c, HPN_E_STATE, "%s before hpn_bam_rmdup_finish", who), nullptr;
-    if (want_finished && u->dead) return fail(c, HPN_E_STATE, "%s: a record lies outside the domain, nothing was decided", who), nullptr;
-    return u;
-}
+namespace {
 
 RmArrays arrays_of(hpn_rmdup_state *u)
 {
@@ -55,15 +49,15 @@ RmArrays arrays_of(hpn_rmdup_state *u)
                     (u64 *)u->hash.p, (u64 *)u->st.soff.p};
 }
 
-// the record the device names: its refID and pos for the caller's message
-int note_bad(hpn_ctx *c, hpn_rmdup_state *u, u64 word)
+// The record the device names, by both of rmdup's kernels that check -- k_rm_classify per batch, k_rm_names in _finish --:
+// 4 reason bits, and its refID and pos for the caller's message from tp[], which holds them by ordinal (rec_add's bad_of).
+int note_bad(hpn_ctx *c, hpn_rmdup_state &u, const uint8_t *, u64 word, uint64_t)
 {
     const uint64_t ord = word >> 4;
     u64 tp = 0;
-    HPN_HIP(c, hipMemcpyAsync(&tp, (const u64 *)u->tp.p + ord, sizeof tp, hipMemcpyDeviceToHost, c->stream));
+    HPN_HIP(c, hipMemcpyAsync(&tp, (const u64 *)u.tp.p + ord, sizeof tp, hipMemcpyDeviceToHost, c->stream));
     HPN_HIP(c, hipStreamSynchronize(c->stream));
-    u->dead = true;
-    u->bad.record = (int64_t)ord, u->bad.tid = (int32_t)(tp >> 32), u->bad.pos = (int32_t)(uint32_t)tp, u->bad.reason = (uint32_t)(word & 15);
+    u.bad.record = (int64_t)ord, u.bad.tid = (int32_t)(tp >> 32), u.bad.pos = (int32_t)(uint32_t)tp, u.bad.reason = (uint32_t)(word & 15);
     return HPN_OK;
 }
 
@@ -113,65 +107,26 @@ int hpn_bam_rmdup_begin(hpn_ctx *c, int32_t n_ref, uint32_t n_ids, const char *c
 int hpn_bam_rmdup_add_raw_dev(hpn_ctx *c, const uint8_t *d_raw, hpn_rmdup_info *info)
 {
     if (!c || !info) return HPN_E_ARG;
-    hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_add_raw_dev", false);
+    hpn_rmdup_state *u = rec_live<hpn_rmdup_state>(c, "hpn_bam_rmdup_add_raw_dev", kRecFeeding);
     if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_rmdup_add_raw_dev behind hpn_bam_rmdup_finish");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(info, 0, sizeof *info);
-    const uint64_t n = d_raw ? c->r_n : 0;
-    BamStore &st = u->st;
-    auto report = [&]() { info->n_records = n, info->store_bytes = st.len, bad_report(u->bad, info); };
-    report();
-    if (u->dead || !n) return HPN_OK;
-    if (st.records + n > kMaxRecords) {                // the first record the session cannot take
-        u->dead = true;
-        u->bad.record = (int64_t)kMaxRecords, u->bad.reason = kRsRecords;
-        st.records += n;
-        report();
-        return HPN_OK;
-    }
-    int rc;
-    const uint64_t have = st.records, all = have + n;
-    if ((rc = grow_keep(c, u->tp, all * 8, have * 8)) != HPN_OK || (rc = grow_keep(c, u->cls, all * 4, have * 4)) != HPN_OK ||
-        (rc = grow_keep(c, u->isize, all * 4, have * 4)) != HPN_OK || (rc = grow_keep(c, u->qsum, all * 4, have * 4)) != HPN_OK ||
-        (rc = grow_keep(c, u->lib, all * 4, have * 4)) != HPN_OK || (rc = grow_keep(c, u->hash, all * 8, have * 8)) != HPN_OK ||
-        (rc = bamstore_grow(c, st, n)) != HPN_OK)
-        return rc;
-    const RmIds ids = {(const uint8_t *)u->id_bytes.p, (const uint32_t *)u->id_off.p, (const uint32_t *)u->id_lib.p, u->n_ids};
-    HPN_HIP(c, launch_rmdup_classify(d_raw, (const uint64_t *)c->r_off.p, n, have, st.len, u->n_ref, arrays_of(u), ids, (u64 *)u->info.p, c->stream));
-    u64 h[3];
-    HPN_HIP(c, hipMemcpyAsync(h, u->info.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    if (h[kRmBad] != ~0ull) {
-        st.records = all;
-        if ((rc = note_bad(c, u, h[kRmBad])) != HPN_OK) return rc;
-        report();
-        return HPN_OK;
-    }
-    if ((rc = bamstore_append(c, st, d_raw, h[kRmFirst], h[kRmEnd], n, "hpn_bam_rmdup")) != HPN_OK) return rc;
-    report();
-    return HPN_OK;
+    return rec_add(c, *u, d_raw, info, kRsRecords, {{&u->tp, 8}, {&u->cls, 4}, {&u->isize, 4}, {&u->qsum, 4}, {&u->lib, 4}, {&u->hash, 8}},
+                   [&](uint64_t n, uint64_t base) {
+        const RmIds ids = {(const uint8_t *)u->id_bytes.p, (const uint32_t *)u->id_off.p, (const uint32_t *)u->id_lib.p, u->n_ids};
+        return launch_rmdup_classify(d_raw, (const uint64_t *)c->r_off.p, n, base, u->st.len, u->n_ref, arrays_of(u), ids, (u64 *)u->info.p, c->stream);
+    }, note_bad);
 }
 
 int hpn_bam_rmdup_finish(hpn_ctx *c, hpn_rmdup_result *res)
 {
-    if (!c || !res) return HPN_E_ARG;
-    hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_finish", false);
-    if (!u) return HPN_E_STATE;
-    if (u->finished) return fail(c, HPN_E_STATE, "hpn_bam_rmdup_finish twice");
-    HPN_HIP(c, hipSetDevice(c->device));
-    memset(res, 0, sizeof *res);
-    u->finished = true;
+    hpn_rmdup_state *u;
+    int rc = rec_finish_open(c, "hpn_bam_rmdup_finish", res, u, [](hpn_rmdup_state &s, hpn_rmdup_result *r) { r->n_libs = s.n_libs, r->n_ref = s.n_ref; });
+    if (!u) return rc;
     auto report = [&]() {
-        res->n_records = u->st.records, res->n_out = u->n_out, res->payload_bytes = u->out.payload, res->n_heads = u->n_heads;
+        res->n_out = u->n_out, res->payload_bytes = u->out.payload, res->n_heads = u->n_heads;
         bad_report(u->bad, res);
-        res->n_libs = u->n_libs, res->n_ref = u->n_ref;
     };
-    report();
-    if (u->dead) return HPN_OK;
     const uint64_t n = u->st.records;
-    int rc;
-    Scratch *per_record[] = {&u->rb, &u->hf, &u->rid, &u->evkind, &u->evrec, &u->slot, &u->drop, &u->now, &u->sl, &u->hval, &u->eval, &u->order};
+    Scratch *per_record[] = {&u->rb, &u->hf, &u->rid, &u->evkind, &u->evrec, &u->slot, &u->drop, &u->now, &u->sl, &u->hval, &u->eval, &u->placed};
     for (Scratch *s : per_record)
         if ((rc = need(c, *s, n * 4)) != HPN_OK) return rc;
     Scratch *scanned[] = {&u->rsc, &u->hsc, &u->cnow, &u->cslot, &u->runstart};
@@ -183,7 +138,7 @@ int hpn_bam_rmdup_finish(hpn_ctx *c, hpn_rmdup_result *res)
                       (uint32_t *)u->runstart.p, (uint32_t *)u->evkind.p, (uint32_t *)u->evrec.p, (uint32_t *)u->slot.p, (uint32_t *)u->drop.p,
                       (uint32_t *)u->now.p,    (uint32_t *)u->sl.p,    (uint32_t *)u->cnow.p, (uint32_t *)u->cslot.p};
     u64 *hkey = (u64 *)u->hkey.p, *ekey = (u64 *)u->ekey.p;
-    uint32_t *hval = (uint32_t *)u->hval.p, *eval = (uint32_t *)u->eval.p, *order = (uint32_t *)u->order.p;
+    uint32_t *hval = (uint32_t *)u->hval.p, *eval = (uint32_t *)u->eval.p, *order = (uint32_t *)u->placed.p;
     uint32_t counts[2] = {0, 0};      // runs, heads
     if (n) {
         // runs and heads
@@ -213,7 +168,8 @@ int hpn_bam_rmdup_finish(hpn_ctx *c, hpn_rmdup_result *res)
         HPN_HIP(c, hipMemcpyAsync(&bad, u->info.p, sizeof bad, hipMemcpyDeviceToHost, c->stream));
         HPN_HIP(c, hipStreamSynchronize(c->stream));
         if (bad != ~0ull) {
-            if ((rc = note_bad(c, u, bad)) != HPN_OK) return rc;
+            if ((rc = note_bad(c, *u, nullptr, bad, 0)) != HPN_OK) return rc;
+            u->dead = true;
             report();
             return HPN_OK;
         }
@@ -230,6 +186,7 @@ int hpn_bam_rmdup_finish(hpn_ctx *c, hpn_rmdup_result *res)
         HPN_HIP(c, hipMemsetAsync(order, 0, n * 4, c->stream));          // (every entry is written below; an ordinal in any case)
         HPN_HIP(c, launch_rmdup_place(W, n, u->n_out, order, c->stream));
     }
+    u->order = order;
     if ((rc = sliceout_offsets(c, u->out, u->st, order, u->n_out, false, "hpn_bam_rmdup")) != HPN_OK) return rc;
     report();
     return HPN_OK;
@@ -238,7 +195,7 @@ int hpn_bam_rmdup_finish(hpn_ctx *c, hpn_rmdup_result *res)
 int hpn_bam_rmdup_counts(hpn_ctx *c, hpn_rmdup_lib *libs, hpn_rmdup_target *targets)
 {
     if (!c || !libs || !targets) return HPN_E_ARG;
-    hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_counts", true);
+    hpn_rmdup_state *u = rec_live<hpn_rmdup_state>(c, "hpn_bam_rmdup_counts", kRecFinished);
     if (!u) return HPN_E_STATE;
     HPN_HIP(c, hipSetDevice(c->device));
     const size_t nt = (size_t)u->n_ref + 1;
@@ -256,48 +213,27 @@ int hpn_bam_rmdup_counts(hpn_ctx *c, hpn_rmdup_lib *libs, hpn_rmdup_target *targ
 
 int hpn_bam_rmdup_order(hpn_ctx *c, uint32_t *order, uint64_t n)
 {
-    if (!c || (n && !order)) return HPN_E_ARG;
-    hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_order", true);
-    if (!u) return HPN_E_STATE;
-    if (n != u->n_out) return fail(c, HPN_E_ARG, "hpn_bam_rmdup_order: %llu entries asked for, %llu records survive", (unsigned long long)n,
-                                   (unsigned long long)u->n_out);
-    if (!n) return HPN_OK;
-    HPN_HIP(c, hipSetDevice(c->device));
-    HPN_HIP(c, hipMemcpyAsync(order, u->order.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HPN_HIP(c, hipStreamSynchronize(c->stream));
-    return HPN_OK;
+    return rec_order<hpn_rmdup_state>(c, "hpn_bam_rmdup_order", order, n);
 }
 
 int hpn_bam_rmdup_emit(hpn_ctx *c, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info)
 {
-    if (!c || !info) return HPN_E_ARG;
-    hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_emit", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_emit(c, u->out, u->st, (const uint32_t *)u->order.p, u->n_out, first_record, max_records, last, info, "hpn_bam_rmdup");
+    return rec_emit<hpn_rmdup_state>(c, "hpn_bam_rmdup_emit", first_record, max_records, last, info);
 }
 
 int hpn_bam_rmdup_blocks(hpn_ctx *c, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n)
 {
-    if (!c || !n) return HPN_E_ARG;
-    hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_blocks", true);
-    if (!u) return HPN_E_STATE;
-    return list_blocks(c, u->out.list, first, out, cap, n);
+    return rec_blocks<hpn_rmdup_state>(c, "hpn_bam_rmdup_blocks", first, out, cap, n);
 }
 
 int hpn_bam_rmdup_payload_dev(hpn_ctx *c, const uint8_t **d_payload, uint64_t *n_bytes)
 {
-    if (!c || !d_payload || !n_bytes) return HPN_E_ARG;
-    hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_payload_dev", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_payload(u->out, d_payload, n_bytes);
+    return rec_payload<hpn_rmdup_state>(c, "hpn_bam_rmdup_payload_dev", d_payload, n_bytes);
 }
 
 int hpn_bam_rmdup_stored_dev(hpn_ctx *c, const uint8_t **d_image, uint64_t *n_bytes)
 {
-    if (!c || !d_image || !n_bytes) return HPN_E_ARG;
-    hpn_rmdup_state *u = live(c, "hpn_bam_rmdup_stored_dev", true);
-    if (!u) return HPN_E_STATE;
-    return sliceout_stored(c, u->out, d_image, n_bytes);
+    return rec_stored<hpn_rmdup_state>(c, "hpn_bam_rmdup_stored_dev", d_image, n_bytes);
 }
 
 }  // extern "C"

@@ -19,6 +19,8 @@
 
 using namespace hpn;
 
+static const SliceCalls kCalls = {"hpn_bam_rmdup", "bam_rmdup", hpn_bam_rmdup_emit, hpn_bam_rmdup_blocks, hpn_bam_rmdup_payload_dev, hpn_bam_rmdup_stored_dev};
+
 // 0 the output is written, 1 not for the device (the host route starts over; nothing has been said, no output is left)
 static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
 {
@@ -44,41 +46,19 @@ static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
     int rc = hpn_bam_rmdup_begin(ctx, (int32_t)hdr.name.size(), (uint32_t)ids.size(), ids.data(), lib_of_id.data(), (uint32_t)lib_name.size());
     if (rc == HPN_E_ARG || rc == HPN_E_NOMEM) return 1;       // (more IDs than the table takes)
     if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_begin");
-    double t_ingest = 0, t_store = 0, t_decide = 0, t0;
-    uint64_t n_batches = 0;
-    auto outside = [&](long long rec, int tid, int pos, unsigned reason) {
-        if (timing) fprintf(stderr, "[hpn] bam_rmdup: record %lld (refID %d, pos %d) is outside the device's domain (reason %u)\n", rec, tid, pos, reason);
-        return 1;
-    };
-    const bool fed = each_batch(bam, &t_ingest, [&](const BgzfDevice &) {
-        hpn_rmdup_info ri;
-        t0 = wall_s();
-        rc = hpn_bam_rmdup_add_raw_dev(ctx, bam.d_raw(), &ri);
-        if (rc == HPN_E_NOMEM) return false;               // the working set does not fit the device
-        if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_add_raw_dev");
-        t_store += wall_s() - t0, ++n_batches;
-        if (ri.bad_record >= 0) return outside((long long)ri.bad_record, ri.bad_tid, ri.bad_pos, ri.reason) == 0;
-        return true;
-    });
-    if (!fed) return 1;
+    FeedRun fed;
+    if (!feed_session(ctx, bam, kCalls, hpn_bam_rmdup_add_raw_dev, timing, fed)) return 1;
     hpn_rmdup_result res;
-    t0 = wall_s();
-    rc = hpn_bam_rmdup_finish(ctx, &res);
-    if (rc == HPN_E_NOMEM) return 1;
-    if (rc != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_finish");
-    if (res.bad_record >= 0) return outside((long long)res.bad_record, res.bad_tid, res.bad_pos, res.reason);
+    const double t0 = wall_s();
+    if (!finish_session(ctx, kCalls, hpn_bam_rmdup_finish, timing, res)) return 1;
     std::vector<hpn_rmdup_lib> libs(lib_name.size());
     std::vector<hpn_rmdup_target> targets(hdr.name.size() + 1);
     if ((rc = hpn_bam_rmdup_counts(ctx, libs.data(), targets.data())) != HPN_OK) die_hpn(ctx, rc, "hpn_bam_rmdup_counts");
-    t_decide = wall_s() - t0;
-    const std::vector<uint8_t> head = hdr.bytes();
-    std::vector<uint8_t> head_blocks;
-    if (!bgzf_plain_blocks(head.data(), head.size(), -1, head_blocks)) return 1;
+    const double t_decide = wall_s() - t0;
     BgzfWriter writer(-1);
     SliceRun run;
-    const SliceCalls calls = {"hpn_bam_rmdup", hpn_bam_rmdup_emit, hpn_bam_rmdup_blocks, hpn_bam_rmdup_payload_dev, hpn_bam_rmdup_stored_dev};
     // (the output is a file: whenever the device's memory runs out it can go, and the host route makes it again)
-    const int ws = write_slices(ctx, calls, res.n_out, -1, writer, false, [&]() {
+    const int ws = write_session(ctx, kCalls, hdr, res.n_out, -1, writer, o.out, false, "[hpn] bam_rmdup", [&](const std::vector<uint8_t> &head_blocks) {
         if (!writer.begin(o.out, head_blocks)) {
             fputs(said.c_str(), stderr);
             fputs("[bam_rmdup] fail to read/write input files\n", stderr);
@@ -86,14 +66,7 @@ static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
         }
         return true;
     }, run);
-    if (ws == kSlicesNoMem) {   // the output so far goes; the host route makes it again
-        if (run.created) writer.abandon(), unlink(o.out);
-        return 1;
-    }
-    if (!writer.finish()) {
-        fprintf(stderr, "[hpn] bam_rmdup: writing %s failed\n", o.out);
-        leave(2);
-    }
+    if (ws != kSlicesDone) return 1;
     // the reference's words, now that nothing can send the file to the host any more: per target that has records what the
     // target before left in the set, then "processing reference"; the same check where the unplaced records begin; the libraries
     // in the order of khash's buckets, entered as their first heads came
@@ -120,31 +93,20 @@ static int rmdup_device(hpn_ctx *ctx, const rmdup::Options &o, bool timing)
         fprintf(stderr, "[hpn] bam_rmdup: inflate + record index %.3f s, classify + store %.3f s, groups + names + placement %.3f s, gather + cuts + crc %.3f s, "
                         "copies to the host %.3f s, handing to the writer %.3f s; %llu batches, %llu records in, %llu heads, %llu records out, %llu blocks; "
                         "writer: %.3f s deflating (all threads), %.3f s waited for\n",
-                t_ingest, t_store, t_decide, run.t_emit, run.t_copy, run.t_hand, (unsigned long long)n_batches, (unsigned long long)res.n_records,
+                fed.t_ingest, fed.t_store, t_decide, run.t_emit, run.t_copy, run.t_hand, (unsigned long long)fed.n_batches, (unsigned long long)res.n_records,
                 (unsigned long long)res.n_heads, (unsigned long long)res.n_out, (unsigned long long)run.n_blocks, writer.deflate_seconds(), writer.waited_seconds());
     return 0;
 }
 
 int main(int argc, char *argv[])
 {
-    bind_before_runtime();
-    stamp("main");
     rmdup::Options o;
-    if (!rmdup::parse_args(argc, argv, o)) return 1;
-    const bool timing = getenv("HPN_TIMING") != nullptr;
-    if (bam_gpu_enabled() && !o.se && strcmp(o.in, "-") != 0 && strcmp(o.out, "-") != 0 && access(o.in, R_OK) == 0) {
-        hpn_ctx *ctx = open_tool_ctx();
-        stamp("context created");
-        const int r = rmdup_device(ctx, o, timing);
-        if (timing) fprintf(stderr, "[hpn] bam_rmdup: %s\n", r == 0 ? "device route" : "device route abandoned: host route");
-        if (r == 0) {
-            stamp("finished");
-            quick_exit_ok();
-        }
-    } else if (timing) {
-        fprintf(stderr, "[hpn] bam_rmdup: host route\n");
-    }
-    const int status = rmdup::rmdup_on_host(o);
-    stamp("finished");
-    leave(status);
+    return run_tool(
+        "bam_rmdup",
+        [&]() { return rmdup::parse_args(argc, argv, o) ? 0 : 1; },
+        [&]() {
+            return bam_gpu_enabled() && !o.se && strcmp(o.in, "-") != 0 && strcmp(o.out, "-") != 0 && access(o.in, R_OK) == 0;
+        },
+        [&](hpn_ctx *ctx, bool timing) { return rmdup_device(ctx, o, timing); },
+        [&]() { return rmdup::rmdup_on_host(o); });
 }

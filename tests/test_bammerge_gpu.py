@@ -11,21 +11,19 @@ bam2depth."""
 import os
 import struct
 import subprocess
-import zlib
 
 import numpy as np
 import pytest
 
-import bam_layouts as BL
 import bammerge_inputs
 import bammerge_ref
 import bamsort_ref
+from bam_session import blocks_of_records, emit_all, every_boundary_and_inside, feed
 from conftest import BIN, GOLDEN, HOOKS_BIN
 from split_cases import stop_on_fault
 from test_bammerge_golden import CASES, MANIFEST, check_run, lay_out
 
 pytestmark = pytest.mark.gpu
-FULL = bamsort_ref.FULL
 TOOL = os.path.join(BIN, "bam_merge")
 EMPTY = bammerge_ref.EMPTY
 
@@ -110,66 +108,6 @@ def test_the_tool_with_one_small_chunk_a_launch(sets, tmp_path, cid):
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------
 
-def feed(ctx, stream, cuts):
-    """the records of one file's `stream` through hpn_bam_merge_add_raw_dev in batches that end at the stream offsets `cuts`; the
-    last BamMergeInfo"""
-    import torch
-    cuts = sorted({c for c in cuts if 0 < c < len(stream)} | {len(stream)}) if stream else []
-    front, at, info = b"", 0, None
-    for end in cuts:
-        piece = stream[at:end]
-        at = end
-        members = [BL.bgzf_member(piece[i:i + 60000], 1) for i in range(0, len(piece), 60000)]
-        table, comp, outo = np.zeros((len(members), 3), np.uint64), [], len(front)
-        pos = 0
-        for k, mem in enumerate(members):
-            a, n, isz = BL.blocks(mem)[0]
-            table[k] = (pos + a, n | (isz << 32), outo)
-            comp.append(mem)
-            pos += len(mem)
-            outo += isz
-        nb = len(members)
-        d_comp = torch.from_numpy(np.frombuffer(b"".join(comp) + bytes(64), np.uint8).copy()).cuda()
-        d_blocks = torch.from_numpy(table.view(np.int64)).cuda()
-        d_out = torch.zeros(outo + 64, dtype=torch.uint8, device="cuda")
-        if front:
-            d_out[:len(front)] = torch.from_numpy(np.frombuffer(front, np.uint8).copy()).cuda()
-        d_status = torch.zeros(nb, dtype=torch.int32, device="cuda")
-        torch.cuda.synchronize()
-        ctx.bgzf_inflate_dev(d_comp, d_blocks, nb, d_out, d_status)
-        raw = ctx.bam_raw_index_dev(d_out, d_blocks, nb, 0, d_status)
-        assert raw.flags & 3 == 0, raw.flags
-        whole = front + piece
-        front = whole[len(whole) - raw.tail_bytes:] if raw.tail_bytes else b""
-        if raw.n_records:
-            info = ctx.bam_merge_add_raw_dev(d_out)
-            if info.bad_record >= 0:
-                return info
-    assert front == b""
-    return info
-
-
-def emit_all(ctx, n, slice_records):
-    """the merged output in slices -> [(payload, crc)] of every block"""
-    blocks, first = [], 0
-    while True:
-        cnt = min(slice_records, n - first)
-        last = first + cnt == n
-        info = ctx.bam_merge_emit(first, cnt, last)
-        assert info.n_records == cnt and info.bad_record == -1
-        bl = ctx.bam_merge_blocks(info.n_blocks)
-        assert len(bl) == info.n_blocks
-        pay = ctx.bam_merge_payload()
-        assert len(pay) == info.payload_bytes
-        for b in bl:
-            assert b.tid == 0 and 0 < b.len <= FULL and b.off + b.len <= len(pay)
-            blocks.append((pay[b.off:b.off + b.len], b.crc))
-        assert (info.open_bytes == 0) if last else (info.open_bytes < FULL)
-        first += cnt
-        if last:
-            return blocks
-
-
 def abi_merge(ctx, streams, cuts=(), slice_records=1 << 30, emit=True):
     """streams: per file the bytes of its records.  -> (BamMergeResult, order, blocks)"""
     import highperformancengs_amd as hp
@@ -177,12 +115,12 @@ def abi_merge(ctx, streams, cuts=(), slice_records=1 << 30, emit=True):
         ctx.bam_merge_begin()
         for s in streams:
             ctx.bam_merge_next_file()
-            info = feed(ctx, s, cuts)
+            info = feed(ctx, ctx.bam_merge_add_raw_dev, s, cuts)
             assert info is None or info.bad_record == -1
         res = ctx.bam_merge_finish()
         assert (res.n_files, res.bad_record, res.payload_bytes) == (len(streams), -1, sum(len(s) for s in streams))
         order = ctx.bam_merge_order(res.n_records)
-        return res, order, emit_all(ctx, res.n_records, slice_records) if emit else None
+        return res, order, emit_all(ctx, "merge", res.n_records, slice_records)[0] if emit else None
     except hp.HpnError as e:
         stop_on_fault(0, str(e))
         raise
@@ -194,16 +132,7 @@ def restated(recs):
     base = [sum(len(f) for f in recs[:k]) for k in range(len(recs))]
     order, lifted = bammerge_ref.effective_order(keys)
     assert order == bammerge_ref.heap_order(keys)
-    pieces = bamsort_ref.cut(b"", [recs[f][i] for f, i in order])
-    return [base[f] + i for f, i in order], lifted, [(p, zlib.crc32(p) & 0xffffffff) for p in pieces]
-
-
-def every_boundary_and_inside(recs):
-    cuts, at = set(), 0
-    for r in recs:
-        cuts |= {at + 1, at + 9, at + len(r) // 2, at + len(r) - 1, at + len(r)}
-        at += len(r)
-    return cuts
+    return [base[f] + i for f, i in order], lifted, blocks_of_records([recs[f][i] for f, i in order])
 
 
 @pytest.mark.parametrize("name", ["three_sorted", "unsorted_all", "pos_high", "empty_middle", "empty_first", "empty_last", "equal_keys"])
@@ -375,7 +304,7 @@ def test_abi_names_the_heap_empty_record(ctx, file_at, later_batch):
         info = None
         for k, (a, _) in enumerate(files[:file_at + 1]):
             ctx.bam_merge_next_file()
-            info = feed(ctx, a.tobytes(), {20 * 37, 30 * 37 + 5} if later_batch else set())
+            info = feed(ctx, ctx.bam_merge_add_raw_dev, a.tobytes(), {20 * 37, 30 * 37 + 5} if later_batch else set())
             assert (info.bad_record >= 0) == (k == file_at)
         ordinal = 50 * file_at + at
         assert (info.bad_record, info.bad_tid, info.bad_pos, info.reason) == (ordinal, -1, pos, 1)
@@ -407,7 +336,7 @@ def test_abi_session_order_is_checked():
         assert state(e)
         c.bam_merge_next_file()
         arr, _ = minimal([0, 0], [5, 3], [0, 0])
-        feed(c, arr.tobytes(), set())
+        feed(c, c.bam_merge_add_raw_dev, arr.tobytes(), set())
         c.bam_merge_next_file()
         res = c.bam_merge_finish()
         assert (res.n_records, res.n_files, res.n_lifted, res.bad_record) == (2, 2, 1, -1)

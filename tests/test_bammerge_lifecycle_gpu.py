@@ -6,7 +6,8 @@ import pytest
 import bammerge_inputs
 import bammerge_ref
 import bamsort_ref
-from test_bammerge_gpu import emit_all, feed, restated
+from bam_session import emit_all, feed
+from test_bammerge_gpu import restated
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +32,7 @@ def fed(ctx, files, upto=None):
     for f in files[:upto]:
         ctx.bam_merge_next_file()
         stream = b"".join(f)
-        feed(ctx, stream, {len(stream) // 2 + 3})
+        feed(ctx, ctx.bam_merge_add_raw_dev, stream, {len(stream) // 2 + 3})
 
 
 def test_context_closed_after_one_file(files):
@@ -66,7 +67,7 @@ def test_begin_one_file_begin_again_then_a_whole_session(files):
         res = c.bam_merge_finish()
         assert (res.n_records, res.n_files, res.n_lifted, res.bad_record) == (len(want_order), 3, lifted, -1)
         assert list(c.bam_merge_order(res.n_records)) == want_order
-        assert emit_all(c, res.n_records, 50) == want
+        assert emit_all(c, "merge", res.n_records, 50)[0] == want
         image = c.bam_merge_stored()      # the last slice's blocks framed for level 0
         assert image.endswith(bamsort_ref.member(want[-1][0], 0))
     finally:

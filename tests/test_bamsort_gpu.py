@@ -18,9 +18,9 @@ import numpy as np
 import pytest
 
 import bai_ref
-import bam_layouts as BL
 import bamsort_inputs
 import bamsort_ref
+from bam_session import emit_all, every_boundary_and_inside, expected_blocks, feed
 from conftest import BIN, GOLDEN, HOOKS_BIN, in_hooks_build
 from split_cases import stop_on_fault
 from test_bamsort_golden import CASES, MANIFEST, check_bam
@@ -114,98 +114,21 @@ def test_the_tool_with_one_small_chunk_a_launch(made, tmp_path, cid):
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------
 
-def feed(ctx, stream, cuts):
-    """the records of `stream` through hpn_bam_sort_add_raw_dev in batches that end at the stream offsets `cuts`; the last
-    BamSortInfo"""
-    import torch
-    cuts = sorted({c for c in cuts if 0 < c < len(stream)} | {len(stream)}) if stream else []
-    front, at, info = b"", 0, None
-    for end in cuts:
-        piece = stream[at:end]
-        at = end
-        members = [BL.bgzf_member(piece[i:i + 60000], 1) for i in range(0, len(piece), 60000)]
-        table, comp, outo = np.zeros((len(members), 3), np.uint64), [], len(front)
-        pos = 0
-        for k, mem in enumerate(members):
-            a, n, isz = BL.blocks(mem)[0]
-            table[k] = (pos + a, n | (isz << 32), outo)
-            comp.append(mem)
-            pos += len(mem)
-            outo += isz
-        nb = len(members)
-        d_comp = torch.from_numpy(np.frombuffer(b"".join(comp) + bytes(64), np.uint8).copy()).cuda()
-        d_blocks = torch.from_numpy(table.view(np.int64)).cuda()
-        d_out = torch.zeros(outo + 64, dtype=torch.uint8, device="cuda")
-        if front:
-            d_out[:len(front)] = torch.from_numpy(np.frombuffer(front, np.uint8).copy()).cuda()
-        d_status = torch.zeros(nb, dtype=torch.int32, device="cuda")
-        torch.cuda.synchronize()
-        ctx.bgzf_inflate_dev(d_comp, d_blocks, nb, d_out, d_status)
-        raw = ctx.bam_raw_index_dev(d_out, d_blocks, nb, 0, d_status)
-        assert raw.flags & 3 == 0, raw.flags
-        whole = front + piece
-        front = whole[len(whole) - raw.tail_bytes:] if raw.tail_bytes else b""
-        if raw.n_records:
-            info = ctx.bam_sort_add_raw_dev(d_out)
-            if info.bad_record >= 0:
-                return info
-    assert front == b""
-    return info
-
-
-def emit_all(ctx, n, slice_records, stored=False):
-    """the sorted output in slices -> ([(payload, crc)] of every block, the stored image)"""
-    blocks, image, first = [], b"", 0
-    while True:
-        cnt = min(slice_records, n - first)
-        last = first + cnt == n
-        info = ctx.bam_sort_emit(first, cnt, last)
-        assert info.n_records == cnt and info.bad_record == -1
-        bl = ctx.bam_sort_blocks(info.n_blocks)
-        assert len(bl) == info.n_blocks
-        pay = ctx.bam_sort_payload()
-        assert len(pay) == info.payload_bytes
-        for b in bl:
-            assert b.tid == 0 and 0 < b.len <= FULL and b.off + b.len <= len(pay)
-            blocks.append((pay[b.off:b.off + b.len], b.crc))
-        if stored:
-            img = ctx.bam_sort_stored()
-            assert len(img) == sum(b.len + 31 for b in bl)
-            image += img
-        assert (info.open_bytes == 0) if last else (info.open_bytes < FULL)
-        first += cnt
-        if last:
-            return blocks, image
-
-
 def abi_sort(ctx, recs, cuts, slice_records=1 << 30, stored=False):
     import highperformancengs_amd as hp
     try:
         ctx.bam_sort_begin()
-        info = feed(ctx, b"".join(recs), cuts)
+        info = feed(ctx, ctx.bam_sort_add_raw_dev, b"".join(recs), cuts)
         assert info is None or info.bad_record == -1
         res = ctx.bam_sort_finish()
         assert (res.n_records, res.bad_record, res.payload_bytes) == (len(recs), -1, sum(len(r) for r in recs))
         order = ctx.bam_sort_order(res.n_records)
         sizes = ctx.bam_sort_sizes(res.n_records)
-        blocks, image = emit_all(ctx, res.n_records, slice_records, stored)
+        blocks, image = emit_all(ctx, "sort", res.n_records, slice_records, stored)
         return res, order, sizes, blocks, image
     except hp.HpnError as e:
         stop_on_fault(0, str(e))
         raise
-
-
-def expected_blocks(recs, order):
-    pieces = bamsort_ref.cut(b"", [recs[i] for i in order])
-    return [(p, zlib.crc32(p) & 0xffffffff) for p in pieces]
-
-
-def every_boundary_and_inside(recs):
-    cuts, at = set(), 0
-    for r in recs:
-        cuts |= {at + 1, at + 9, at + len(r) // 2, at + len(r) - 1, at + len(r)}
-        at += len(r)
-    return cuts
 
 
 @pytest.mark.parametrize("name", ["tid_beyond", "targets_3", "unplaced_pos"])
@@ -255,7 +178,7 @@ def test_abi_names_the_first_record_outside_the_domain(ctx, inputs):
         ordinal = next(i for i, r in enumerate(recs) if not bamsort_ref.POS_MIN <= bamsort_ref.fields(r)[1] <= bamsort_ref.POS_MAX)
         for cuts in (set(), every_boundary_and_inside(recs[:ordinal + 2])):
             ctx.bam_sort_begin()
-            info = feed(ctx, b"".join(recs), cuts)
+            info = feed(ctx, ctx.bam_sort_add_raw_dev, b"".join(recs), cuts)
             tid, pos, _ = bamsort_ref.fields(recs[ordinal])
             assert (info.bad_record, info.bad_tid, info.bad_pos, info.reason) == (ordinal, tid, pos, reason)
             res = ctx.bam_sort_finish()
@@ -304,7 +227,7 @@ def test_gather_writes_nothing_outside_its_records(request, ctx, hooks):
     order = np.argsort(bamsort_ref.model_keys(recs), kind="stable")
     out = [recs[i] for i in order]
     ctx.bam_sort_begin()
-    feed(ctx, b"".join(recs), {400000, 1500000})
+    feed(ctx, ctx.bam_sort_add_raw_dev, b"".join(recs), {400000, 1500000})
     res = ctx.bam_sort_finish()
     assert list(ctx.bam_sort_order(res.n_records)) == list(order)
     first, fill, room, model = 0, 0, None, bamsort_ref.cut(b"", out)
@@ -353,7 +276,7 @@ def test_sort_of_133121_records(ctx):
     keys = (tid.astype(np.int64).astype(np.uint64) << np.uint64(32)) | ((pos.astype(np.int64) + 1) << 1).astype(np.uint64) | (flag >> 4).astype(np.uint64)
     want = np.argsort(keys, kind="stable")
     ctx.bam_sort_begin()
-    feed(ctx, arr.tobytes(), {1000003, 3000001})
+    feed(ctx, ctx.bam_sort_add_raw_dev, arr.tobytes(), {1000003, 3000001})
     res = ctx.bam_sort_finish()
     assert (res.n_records, res.payload_bytes, res.bad_record) == (n, 37 * n, -1)
     assert res.sort_bits == 32 + 9                                         # 301 high words: 9 bits of rank

@@ -11,23 +11,21 @@ recorded case runs on the device route and again with HPN_BAM_GPU=0; then the ch
 -> bam_rmdup -> bam_index."""
 import os
 import subprocess
-import zlib
 
 import numpy as np
 import pytest
 
 import bai_ref
-import bam_layouts as BL
 import bamsort_ref
 import fixmate_inputs
 import fixmate_ref
 import rmdup_ref
+from bam_session import blocks_of_records, emit_all, every_boundary_and_inside, feed
 from conftest import BIN, HOOKS_BIN
 from split_cases import stop_on_fault
 from test_fixmate_golden import CASES, MANIFEST, run_case
 
 pytestmark = pytest.mark.gpu
-FULL = bamsort_ref.FULL
 TOOL = os.path.join(BIN, "bam_fixmate")
 
 
@@ -91,76 +89,17 @@ def test_the_tool_with_one_small_chunk_a_launch(inputs, tmp_path, cid):
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------
 
-def feed(ctx, stream, cuts):
-    """the records of `stream` through hpn_bam_fixmate_add_raw_dev in batches that end at the stream offsets `cuts`; the last info"""
-    import torch
-    cuts = sorted({c for c in cuts if 0 < c < len(stream)} | {len(stream)}) if stream else []
-    front, at, info = b"", 0, None
-    for end in cuts:
-        piece = stream[at:end]
-        at = end
-        members = [BL.bgzf_member(piece[i:i + 60000], 1) for i in range(0, len(piece), 60000)]
-        table, comp, outo = np.zeros((len(members), 3), np.uint64), [], len(front)
-        pos = 0
-        for k, mem in enumerate(members):
-            a, n, isz = BL.blocks(mem)[0]
-            table[k] = (pos + a, n | (isz << 32), outo)
-            comp.append(mem)
-            pos += len(mem)
-            outo += isz
-        nb = len(members)
-        d_comp = torch.from_numpy(np.frombuffer(b"".join(comp) + bytes(64), np.uint8).copy()).cuda()
-        d_blocks = torch.from_numpy(table.view(np.int64)).cuda()
-        d_out = torch.zeros(outo + 64, dtype=torch.uint8, device="cuda")
-        if front:
-            d_out[:len(front)] = torch.from_numpy(np.frombuffer(front, np.uint8).copy()).cuda()
-        d_status = torch.zeros(nb, dtype=torch.int32, device="cuda")
-        torch.cuda.synchronize()
-        ctx.bgzf_inflate_dev(d_comp, d_blocks, nb, d_out, d_status)
-        raw = ctx.bam_raw_index_dev(d_out, d_blocks, nb, 0, d_status)
-        assert raw.flags & 3 == 0, raw.flags
-        whole = front + piece
-        front = whole[len(whole) - raw.tail_bytes:] if raw.tail_bytes else b""
-        if raw.n_records:
-            info = ctx.bam_fixmate_add_raw_dev(d_out)
-            if info.bad_record >= 0:
-                return info
-    assert front == b""
-    return info
-
-
-def emit_all(ctx, n, slice_records):
-    """the output in slices -> [(payload, crc)] of every block"""
-    blocks, first = [], 0
-    while True:
-        cnt = min(slice_records, n - first)
-        last = first + cnt == n
-        info = ctx.bam_fixmate_emit(first, cnt, last)
-        assert info.n_records == cnt and info.bad_record == -1
-        bl = ctx.bam_fixmate_blocks(info.n_blocks)
-        assert len(bl) == info.n_blocks
-        pay = ctx.bam_fixmate_payload()
-        assert len(pay) == info.payload_bytes
-        for b in bl:
-            assert 0 < b.len <= FULL and b.off + b.len <= len(pay)
-            blocks.append((pay[b.off:b.off + b.len], b.crc))
-        assert (info.open_bytes == 0) if last else (info.open_bytes < FULL)
-        first += cnt
-        if last:
-            return blocks
-
-
 def abi_fixmate(ctx, recs, target_len, remove, cuts=(), slice_records=1 << 30):
     """-> (FixmateResult, order, blocks)"""
     import highperformancengs_amd as hp
     try:
         ctx.bam_fixmate_begin(remove, target_len)
-        info = feed(ctx, b"".join(recs), cuts)
+        info = feed(ctx, ctx.bam_fixmate_add_raw_dev, b"".join(recs), cuts)
         assert info is None or info.bad_record == -1
         res = ctx.bam_fixmate_finish()
         assert res.bad_record == -1 and res.n_records == len(recs)
         order = ctx.bam_fixmate_order(res.n_out)
-        return res, list(order), emit_all(ctx, res.n_out, slice_records)
+        return res, list(order), emit_all(ctx, "fixmate", res.n_out, slice_records)[0]
     except hp.HpnError as e:
         stop_on_fault(0, str(e))
         raise
@@ -168,8 +107,7 @@ def abi_fixmate(ctx, recs, target_len, remove, cuts=(), slice_records=1 << 30):
 
 def restated(recs, target_len, remove):
     out, n = fixmate_ref.machine(recs, target_len, remove)
-    pieces = bamsort_ref.cut(b"", [r for _, r in out])
-    return [i for i, _ in out], n, [(p, zlib.crc32(p) & 0xffffffff) for p in pieces], sum(len(r) for _, r in out)
+    return [i for i, _ in out], n, blocks_of_records([r for _, r in out]), sum(len(r) for _, r in out)
 
 
 def check_abi(ctx, recs, target_len, remove, cuts=(), slice_records=1 << 30):
@@ -185,14 +123,6 @@ def check_abi(ctx, recs, target_len, remove, cuts=(), slice_records=1 << 30):
 def parsed(data):
     p = fixmate_ref.parse(data)
     return p.recs, [ln for _, ln in p.targets]
-
-
-def every_boundary_and_inside(recs):
-    cuts, at = set(), 0
-    for r in recs:
-        cuts |= {at + 1, at + 9, at + len(r) // 2, at + len(r) - 1, at + len(r)}
-        at += len(r)
-    return cuts
 
 
 DEVICE = sorted(n for n in fixmate_inputs.names() if fixmate_ref.route(fixmate_inputs.own_inputs()[n]) == "device")
@@ -232,7 +162,7 @@ def test_abi_names_the_first_record_outside_the_domain(ctx, inputs):
         recs, tl = parsed(inputs[name])
         bad, reason = fixmate_ref.device_reason(recs, len(tl))
         ctx.bam_fixmate_begin(False, tl)
-        info = feed(ctx, b"".join(recs), cuts)
+        info = feed(ctx, ctx.bam_fixmate_add_raw_dev, b"".join(recs), cuts)
         c = fixmate_ref.core(recs[bad])
         assert (info.bad_record, info.bad_tid, info.bad_pos, info.reason) == (bad, c["tid"], c["pos"], reason), name
         res = ctx.bam_fixmate_finish()
@@ -247,13 +177,13 @@ def test_abi_session_order_is_checked(ctx, inputs):
     ctx.bam_fixmate_begin(False, tl)
     with pytest.raises(hp.HpnError):
         ctx.bam_fixmate_emit(0, 1, True)          # before _finish
-    feed(ctx, b"".join(recs), ())
+    feed(ctx, ctx.bam_fixmate_add_raw_dev, b"".join(recs), ())
     res = ctx.bam_fixmate_finish()
     with pytest.raises(hp.HpnError):
         ctx.bam_fixmate_finish()                  # twice
     with pytest.raises(hp.HpnError):
         ctx.bam_fixmate_emit(1, 1, False)         # not the next slice
-    assert len(emit_all(ctx, res.n_out, 2)) == 1
+    assert len(emit_all(ctx, "fixmate", res.n_out, 2)[0]) == 1
     image = ctx.bam_fixmate_stored()              # the last slice's blocks framed for level 0
     want = b"".join(bamsort_ref.member(p, 0) for p in bamsort_ref.cut(b"", [r for _, r in fixmate_ref.machine(recs, tl, False)[0]]))
     assert image == want

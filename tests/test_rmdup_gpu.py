@@ -10,23 +10,21 @@ import ctypes as C
 import glob
 import os
 import subprocess
-import zlib
 
 import numpy as np
 import pytest
 
 import bai_ref
-import bam_layouts as BL
 import bamsort_inputs
 import bamsort_ref
 import rmdup_inputs
 import rmdup_ref
+from bam_session import emit_all, every_boundary_and_inside, expected_blocks, feed
 from conftest import BIN, HOOKS_BIN
 from split_cases import stop_on_fault
 from test_rmdup_golden import CASES, MANIFEST, check_run
 
 pytestmark = pytest.mark.gpu
-FULL = bamsort_ref.FULL
 TOOL = os.path.join(BIN, "bam_rmdup")
 
 
@@ -53,69 +51,6 @@ def ctx():
 
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------
-
-def feed(ctx, stream, cuts):
-    """the records of `stream` through hpn_bam_rmdup_add_raw_dev in batches that end at the stream offsets `cuts`; the last RmdupInfo"""
-    import torch
-    cuts = sorted({c for c in cuts if 0 < c < len(stream)} | {len(stream)}) if stream else []
-    front, at, info = b"", 0, None
-    for end in cuts:
-        piece = stream[at:end]
-        at = end
-        members = [BL.bgzf_member(piece[i:i + 60000], 1) for i in range(0, len(piece), 60000)]
-        table, comp, outo = np.zeros((len(members), 3), np.uint64), [], len(front)
-        pos = 0
-        for k, mem in enumerate(members):
-            a, n, isz = BL.blocks(mem)[0]
-            table[k] = (pos + a, n | (isz << 32), outo)
-            comp.append(mem)
-            pos += len(mem)
-            outo += isz
-        nb = len(members)
-        d_comp = torch.from_numpy(np.frombuffer(b"".join(comp) + bytes(64), np.uint8).copy()).cuda()
-        d_blocks = torch.from_numpy(table.view(np.int64)).cuda()
-        d_out = torch.zeros(outo + 64, dtype=torch.uint8, device="cuda")
-        if front:
-            d_out[:len(front)] = torch.from_numpy(np.frombuffer(front, np.uint8).copy()).cuda()
-        d_status = torch.zeros(nb, dtype=torch.int32, device="cuda")
-        torch.cuda.synchronize()
-        ctx.bgzf_inflate_dev(d_comp, d_blocks, nb, d_out, d_status)
-        raw = ctx.bam_raw_index_dev(d_out, d_blocks, nb, 0, d_status)
-        assert raw.flags & 3 == 0, raw.flags
-        whole = front + piece
-        front = whole[len(whole) - raw.tail_bytes:] if raw.tail_bytes else b""
-        if raw.n_records:
-            info = ctx.bam_rmdup_add_raw_dev(d_out)
-            if info.bad_record >= 0:
-                return info
-    assert front == b""
-    return info
-
-
-def emit_all(ctx, n, slice_records, stored=False):
-    """the output in slices -> ([(payload, crc)] of every block, the stored image)"""
-    blocks, image, first = [], b"", 0
-    while True:
-        cnt = min(slice_records, n - first)
-        last = first + cnt == n
-        info = ctx.bam_rmdup_emit(first, cnt, last)
-        assert info.n_records == cnt and info.bad_record == -1
-        bl = ctx.bam_rmdup_blocks(info.n_blocks)
-        assert len(bl) == info.n_blocks
-        pay = ctx.bam_rmdup_payload()
-        assert len(pay) == info.payload_bytes
-        for b in bl:
-            assert b.tid == 0 and 0 < b.len <= FULL and b.off + b.len <= len(pay)
-            blocks.append((pay[b.off:b.off + b.len], b.crc))
-        if stored:
-            img = ctx.bam_rmdup_stored()
-            assert len(img) == sum(b.len + 31 for b in bl)
-            image += img
-        assert (info.open_bytes == 0) if last else (info.open_bytes < FULL)
-        first += cnt
-        if last:
-            return blocks, image
-
 
 class Model:
     """what rmdup_ref says of a file, with the libraries numbered as a caller of the ABI numbers them"""
@@ -144,29 +79,17 @@ def abi_rmdup(ctx, model, cuts, slice_records=1 << 30, stored=False):
     import highperformancengs_amd as hp
     try:
         model.begin(ctx)
-        info = feed(ctx, b"".join(model.raw), cuts)
+        info = feed(ctx, ctx.bam_rmdup_add_raw_dev, b"".join(model.raw), cuts)
         assert info is None or info.bad_record == -1, (info.bad_record, info.reason)
         res = ctx.bam_rmdup_finish()
         assert (res.n_records, res.bad_record) == (len(model.raw), -1), (res.bad_record, res.reason)
         order = ctx.bam_rmdup_order(res.n_out)
         libs, targets = ctx.bam_rmdup_counts()
-        blocks, image = emit_all(ctx, res.n_out, slice_records, stored)
+        blocks, image = emit_all(ctx, "rmdup", res.n_out, slice_records, stored)
         return res, list(order), libs, targets, blocks, image
     except hp.HpnError as e:
         stop_on_fault(0, str(e))
         raise
-
-
-def expected_blocks(raw, order):
-    return [(p, zlib.crc32(p) & 0xffffffff) for p in bamsort_ref.cut(b"", [raw[i] for i in order])]
-
-
-def every_boundary_and_inside(recs):
-    cuts, at = set(), 0
-    for r in recs:
-        cuts |= {at + 1, at + 9, at + len(r) // 2, at + len(r) - 1, at + len(r)}
-        at += len(r)
-    return cuts
 
 
 def check_abi(ctx, model, cuts, slice_records=1 << 30, stored=False):
@@ -218,7 +141,7 @@ def test_abi_names_the_first_record_outside_the_domain(ctx, inputs):
         r = model.recs[first[0]]
         for cuts in (set(), every_boundary_and_inside(model.raw[:first[0] + 2])):
             model.begin(ctx)
-            info = feed(ctx, b"".join(model.raw), cuts)
+            info = feed(ctx, ctx.bam_rmdup_add_raw_dev, b"".join(model.raw), cuts)
             res = ctx.bam_rmdup_finish()
             assert (res.bad_record, res.reason) == first, name
             assert (res.bad_tid, res.bad_pos) == ((-1, 0) if r.tid == -1 else (r.tid, r.pos)), name
@@ -262,7 +185,7 @@ def test_gather_writes_nothing_outside_its_records(ctx):
     out = [model.raw[i] for i in want_order]
     assert 4097 + 1025 + 100 < len(out) < len(raw) - 1000
     model.begin(ctx)
-    feed(ctx, b"".join(model.raw), {400000, 900001})
+    feed(ctx, ctx.bam_rmdup_add_raw_dev, b"".join(model.raw), {400000, 900001})
     res = ctx.bam_rmdup_finish()
     assert res.n_out == len(out) and list(ctx.bam_rmdup_order(res.n_out)) == want_order and ctx.bam_rmdup_counts()[0] == want_libs
     first, fill, room, seen = 0, 0, None, []
