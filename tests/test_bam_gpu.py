@@ -273,10 +273,12 @@ def test_window_synthetic(ctx, n, seed, W, sort):
 @pytest.mark.parametrize("cigar", ["150M", "151M", "36M", "75M", "250M", "300M", "16M", "1M", "31M", "33M"])
 @pytest.mark.parametrize("sort", [True, False])
 def test_window_reads_of_one_length(ctx, cigar, sort):
-    """Every read of the batch has the same length: the kernel's lanes then share the records of a step by pieces (P lanes
-    per record) and the next pass's pieces are loaded into LDS while this one is counted -- GC sums against the oracle for
-    piece counts 1 .. 8 and beyond (300 bases: the generic path), odd lengths (padding nibble), whole spans of 1024 records
-    and a ragged last one."""
+    """Every read of the batch has the same length, but 20,011 records over 2.7 Mb at W = 1000 put about eight windows under
+    every pass of 64 records: all 313 passes go to the general kernel, k_window_rest (test_window_paths_host.py pins that).
+    There the lanes share the records of a step by pieces (gc_of_wave_records, P lanes per record) -- GC sums against the
+    oracle for piece counts 1 .. 8 and beyond (300 bases: the generic path), odd lengths (padding nibble), whole spans of 1024
+    records and a ragged last one.  The fast kernel's masks, lane-to-piece map and step counts at every length are held by
+    test_window_paths_gpu.py."""
     refs = [("chrA", 2_000_000), ("chrB", 700_000)]
     soa = make_soa(20_011, refs, 17, sort=sort, cigars=[cigar])
     _window_check(ctx, soa, 1000)
@@ -303,7 +305,10 @@ def test_window_every_nibble_code_and_window_seams(ctx, cigar, W):
 def test_window_every_tail_of_a_span(ctx, n):
     """A wave takes 1,024 records in passes of 64; the last span of a batch is ragged.  A pass's record count must never exceed 64
     (round 4 counted the GC of the records behind a pass twice when 65..109 records were left: found by the hg38-shaped file test
-    on the host route, whose batch ended 68 records into a span)."""
+    on the host route, whose batch ended 68 records into a span).  What these inputs reach is mostly the general kernel: at n = 63,
+    64, 70, 109, 110 and 128 every pass spans several windows and goes to k_window_rest; fast passes with a ragged tail occur at
+    n = 1, 65, 1092, 5220 and 8191 only (tails of 1, 4, 36 and 63 records, all of 150 bases).  Every tail of 1 .. 64 records on the
+    fast kernel, at twelve lengths, is in test_window_paths_gpu.py."""
     refs = [("chrA", 900_000)]
     soa = make_soa(n, refs, 41 + n, sort=True, cigars=["150M"])
     _window_check(ctx, soa, 20000)
