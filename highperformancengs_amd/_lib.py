@@ -200,6 +200,28 @@ class FixmateResult(C.Structure):
                 ("reason", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ViewOpts(C.Structure):
+    _fields_ = [("flag_on", C.c_uint32), ("flag_off", C.c_uint32), ("min_mapq", C.c_uint32), ("min_qlen", C.c_int32), ("qual_scale", C.c_int32),
+                ("subsample", C.c_uint32), ("seed", C.c_uint32), ("threshold", C.c_uint32), ("emit", C.c_uint32), ("flag_style", C.c_uint32),
+                ("n_targets", C.c_int32), ("reserved", C.c_uint32), ("target_names", C.c_void_p), ("target_name_off", C.c_void_p),
+                ("rg_id", C.c_char_p), ("rg_ids", C.POINTER(C.c_char_p)), ("lib_ids", C.POINTER(C.c_char_p)), ("n_rg_ids", C.c_uint32),
+                ("n_lib_ids", C.c_uint32), ("has_rg_ids", C.c_uint32), ("has_library", C.c_uint32), ("reserved2", C.c_uint64 * 4)]
+
+
+class ViewInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
+                ("reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ViewResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_out", C.c_uint64), ("payload_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("bad_record", C.c_int64),
+                ("bad_tid", C.c_int32), ("bad_pos", C.c_int32), ("reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ViewTextInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_bytes", C.c_uint64)]
+
+
 class RmdupInfo(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("store_bytes", C.c_uint64), ("bad_record", C.c_int64), ("bad_tid", C.c_int32), ("bad_pos", C.c_int32),
                 ("reason", C.c_uint32), ("reserved", C.c_uint32)]
@@ -366,6 +388,16 @@ SYMBOLS = [
     ("hpn_bam_fixmate_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("hpn_bam_fixmate_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_fixmate_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_view_begin", _int, [_vp, C.POINTER(ViewOpts)]),
+    ("hpn_bam_view_add_raw_dev", _int, [_vp, _vp, C.POINTER(ViewInfo)]),
+    ("hpn_bam_view_finish", _int, [_vp, C.POINTER(ViewResult)]),
+    ("hpn_bam_view_order", _int, [_vp, _vp, _u64]),
+    ("hpn_bam_view_emit", _int, [_vp, _u64, _u64, _int, C.POINTER(SplitInfo)]),
+    ("hpn_bam_view_blocks", _int, [_vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("hpn_bam_view_payload_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_view_stored_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("hpn_bam_view_text_emit", _int, [_vp, _u64, _u64, C.POINTER(ViewTextInfo)]),
+    ("hpn_bam_view_text_dev", _int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("hpn_bam_rmdup_begin", _int, [_vp, _i32, _u32, _vp, _vp, _u32]),
     ("hpn_bam_rmdup_add_raw_dev", _int, [_vp, _vp, C.POINTER(RmdupInfo)]),
     ("hpn_bam_rmdup_finish", _int, [_vp, C.POINTER(RmdupResult)]),
@@ -421,7 +453,7 @@ def lib():
             raise
         fn.restype = res
         fn.argtypes = args
-    if L.hpn_abi_version() != 17:
+    if L.hpn_abi_version() != 18:
         raise RuntimeError("libhpngs.so ABI version mismatch")
     _lib = L
     return L

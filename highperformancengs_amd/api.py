@@ -1004,6 +1004,62 @@ class Context:
         """The closed blocks of the last bam_fixmate_emit framed as stored BGZF blocks (level 0), copied to the host."""
         return self._dev_span_bytes("hpn_bam_fixmate_stored_dev")
 
+    # ---- samtools view: a BAM's records filtered, as BAM, as SAM text or counted (hpn_bam_view_*) ----
+    VIEW_BAM, VIEW_TEXT, VIEW_COUNT = 0, 1, 2
+
+    def bam_view_begin(self, emit, flag_on=0, flag_off=0, min_mapq=0, min_qlen=0, qual_scale=0, subsample=False, seed=0, threshold=0, flag_style=0,
+                       target_names=(), rg_id=None, rg_ids=None, lib_ids=None):
+        """Opens a session.  emit: VIEW_BAM, VIEW_TEXT or VIEW_COUNT; threshold: ceil(fraction * 2^24) of -s; target_names: the
+        header's names as bytes, for text.  The read-group rule, as bytes: rg_id (-r), rg_ids (-R: a list, empty too), lib_ids (-l:
+        the IDs whose LB is the library, empty too); None: not given."""
+        names = b"".join(target_names)
+        off = np.zeros(len(target_names) + 1, np.uint32)
+        off[1:] = np.cumsum([len(n) for n in target_names], dtype=np.uint64)
+        buf = np.frombuffer(names + b"\0", np.uint8).copy()
+        o = _lib.ViewOpts(flag_on, flag_off, min_mapq, min_qlen, qual_scale, 1 if subsample else 0, seed, threshold, emit, flag_style, len(target_names), 0,
+                          buf.ctypes.data, off.ctypes.data)
+        strings = lambda ids: (C.c_char_p * max(len(ids), 1))(*ids)
+        o.rg_id = rg_id
+        if rg_ids is not None:
+            o.rg_ids, o.n_rg_ids, o.has_rg_ids = strings(list(rg_ids)), len(rg_ids), 1
+        if lib_ids is not None:
+            o.lib_ids, o.n_lib_ids, o.has_library = strings(list(lib_ids)), len(lib_ids), 1
+        self._ck(self.L.hpn_bam_view_begin(self.h, C.byref(o)), "hpn_bam_view_begin")
+
+    def bam_view_add_raw_dev(self, d_raw):
+        """The batch hpn_bam_raw_index_dev indexed last is classified and goes into the session's record store -> ViewInfo."""
+        return self._raw_add("hpn_bam_view_add_raw_dev", _lib.ViewInfo, d_raw)
+
+    def bam_view_finish(self):
+        """Decides -> ViewResult (records in, records kept -- the count --, their bytes as BAM or as text, the first record outside the domain)."""
+        return self._finish("hpn_bam_view_finish", _lib.ViewResult)
+
+    def bam_view_order(self, n):
+        """order[j]: the session ordinal of the j-th kept record (n = ViewResult.n_out)."""
+        return self._order("hpn_bam_view_order", n)
+
+    def bam_view_emit(self, first_record, max_records, last=False):
+        """The next slice of a VIEW_BAM session's output, cut into blocks with their CRC-32 -> SplitInfo."""
+        return self._emit("hpn_bam_view_emit", first_record, max_records, last)
+
+    def bam_view_blocks(self, n):
+        """The n closed blocks of the last bam_view_emit -> list of SplitBlock (off, len, crc, tid)."""
+        return self._last_blocks("hpn_bam_view_blocks", n)
+
+    def bam_view_payload(self):
+        """The payload buffer of the last bam_view_emit up to the end of its last closed block, copied to the host."""
+        return self._dev_span_bytes("hpn_bam_view_payload_dev")
+
+    def bam_view_stored(self):
+        """The closed blocks of the last bam_view_emit framed as stored BGZF blocks (level 0), copied to the host."""
+        return self._dev_span_bytes("hpn_bam_view_stored_dev")
+
+    def bam_view_text(self, first_record, max_records):
+        """The next slice of a VIEW_TEXT session's lines -> (ViewTextInfo, the lines' bytes copied to the host)."""
+        info = _lib.ViewTextInfo()
+        self._ck(self.L.hpn_bam_view_text_emit(self.h, int(first_record), int(max_records), C.byref(info)), "hpn_bam_view_text_emit")
+        return info, self._dev_span_bytes("hpn_bam_view_text_dev")
+
     # ---- collectives / synthetic -----------------------------------------
     def comm_init(self, rank, n_ranks, unique_id: bytes):
         buf = (C.c_uint8 * _lib.UNIQUE_ID_BYTES).from_buffer_copy(unique_id)

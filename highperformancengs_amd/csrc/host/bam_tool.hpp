@@ -1,5 +1,5 @@
 // bam_tool.hpp -- what the BAM tools over a device session do alike: the header read on the host, the loop over the stream's
-// batches (bam_index too), and for the record-store sessions (bam_sort, bam_rmdup, bam_merge, bam_fixmate) the batches into the
+// batches (bam_index too), and for the record-store sessions (bam_sort, bam_rmdup, bam_merge, bam_fixmate, bam_view) the batches into the
 // session, its _finish, the way from its slices to the BGZF writer, and main()'s choice between the device and the host route.
 #pragma once
 #include "bam_gpu.hpp"

@@ -6,7 +6,7 @@
 //               records are not the stored ones byte for byte (fixmate) gives `extra` -- output record j takes
 //               size[order[j]] + extra[order[j]] bytes -- and `patch`, which runs on the gathered slice in front of the cuts and
 //               the CRC-32; without the two the slices are what they were;
-//   RecSession  the three and the life cycle around them (sort, rmdup, merge, fixmate): _begin, batches until _finish, then the
+//   RecSession  the three and the life cycle around them (sort, rmdup, merge, fixmate, view): _begin, batches until _finish, then the
 //               output's slices; a record outside the domain kills the session and every later call says so.  rec_live is the one
 //               check of that cycle, rec_add the batch around a family's kernel, rec_finish_open the head of _finish, and
 //               rec_order / rec_emit / rec_blocks / rec_payload / rec_stored the bodies behind a finished session's calls.

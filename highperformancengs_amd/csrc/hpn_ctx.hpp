@@ -54,7 +54,7 @@ struct Scratch {
 struct FamilyState {
     virtual ~FamilyState() = default;
 };
-enum { kStUniq = 0, kStSort, kStUniqq, kStUsort, kStTwobit, kStPair, kStMrle, kStRfastqc, kStSplit, kStKseq, kStBai, kStBamSort, kStBamRmdup, kStBamMerge, kStBamFixmate, kStCount };
+enum { kStUniq = 0, kStSort, kStUniqq, kStUsort, kStTwobit, kStPair, kStMrle, kStRfastqc, kStSplit, kStKseq, kStBai, kStBamSort, kStBamRmdup, kStBamMerge, kStBamFixmate, kStBamView, kStCount };
 
 enum { kFamTally = 0, kFamTrim = 1, kFamDepth = 2, kFamWindow = 3, kFamText = 4, kFamInflate = 5, kFamRaw = 6, kFamRawFields = 7, kFamCount = 8 };
 

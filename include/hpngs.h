@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HPN_ABI_VERSION 17
+#define HPN_ABI_VERSION 18
 #define HPN_LEN_BINS 512   /* SeqLen[512]       fastq_count.c:111 */
 #define HPN_QUAL_ROWS 128  /* Quality[128][512] fastq_count.c:110 */
 #define HPN_NUC_CODES 5    /* T,C,A,G,N         Rgzfastq_uniq.c:97-108 */
@@ -1278,6 +1278,83 @@ int hpn_bam_fixmate_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_recor
 int hpn_bam_fixmate_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
 int hpn_bam_fixmate_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
 int hpn_bam_fixmate_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
+
+/* ---- samtools view: a BAM's records filtered, as BAM, as SAM text or counted ----------------------
+ * sam_view.c (samtools-0.1.19), process_aln: a record is dropped where the CIGAR's query length (ops whose type has bit 1, and H)
+ * is below min_qlen (> 0), mapq < min_mapq, (flag & flag_on) != flag_on, flag & flag_off, or, with subsample, where
+ * ((X31(name) + seed) & 0xffffff) >= threshold -- X31 = __ac_X31_hash_string over signed chars, threshold the 24-bit integer the
+ * caller derives from the fraction: ceil(frac * 2^24), at most 2^24.  qual_scale > 1 turns every quality byte q into
+ * min(q * scale, 93), in BAM and in text output alike.  Text is bam_format1_core's line (bam.c) and a newline, the flag decimal,
+ * 0x%x or by bam_flag2char_table.  The order is the input's.  (docs/kernels/bam_view.md)
+ *   hpn_bam_view_begin(&opts)             the rules, what the session emits and, for text, the targets' names (copied)
+ *   per batch: hpn_bam_raw_index_dev(...), then hpn_bam_view_add_raw_dev(d_raw, &info): the batch's records are classified and
+ *              copied into the session's record store on the device; d_raw NULL: no records
+ *   hpn_bam_view_finish(&res)             res.n_out records are kept: the count.  payload_bytes their bytes as BAM (HPN_VIEW_BAM),
+ *                                         text_bytes their lines' bytes (HPN_VIEW_TEXT)
+ *   hpn_bam_view_order(order, n)          order[j]: the session ordinal of the j-th kept record (n = res.n_out)
+ *   HPN_VIEW_BAM:  hpn_bam_view_emit / _blocks / _payload_dev / _stored_dev    as hpn_bam_sort_emit and its three readers
+ *   HPN_VIEW_TEXT: hpn_bam_view_text_emit(first_record, max_records, &info) formats output records [first, first + n) -- the
+ *                  next ones: first is where the call before ended -- into a device buffer, hpn_bam_view_text_dev(&d_text,
+ *                  &n_bytes) names it until the next call
+ *   The read-group rule (-r, -R, -l): one lane walks the aux fields to RG as bam_aux_get does and compares the value with the
+ *   ID table of hpn_view_opts; the caller derives lib_ids from the header's @RG lines (ID -> LB).
+ *   A BAM call on a text or count session, and a text call on any other, returns HPN_E_STATE.
+ * Domain, where the record's inside is read (text: all of it; -m, -s, qual_scale and the read-group rule: what they read): no f, d or B:f aux field
+ * (reason 1), no A field of value 0 (2), a name whose first NUL is its last byte (3), known aux types and B counts >= 0 (4),
+ * name, CIGAR, sequence, qualities and every aux field inside the record (5), pos and mpos below 2^31 - 1 (6), fewer than 2^31
+ * records (7), refID and mate refID < n_targets (8), CIGAR ops 0..9 (9).  The first record outside it is reported -- bad_record
+ * (session ordinal, -1: none), bad_tid, bad_pos, reason -- and nothing is emitted: the caller works on the host
+ * (csrc/host/bam_view_host.hpp).  A call out of this order returns HPN_E_STATE.  Synchronous. */
+#define HPN_VIEW_BAM 0
+#define HPN_VIEW_TEXT 1
+#define HPN_VIEW_COUNT 2
+typedef struct hpn_view_opts {
+    uint32_t flag_on, flag_off, min_mapq;
+    int32_t min_qlen, qual_scale;
+    uint32_t subsample, seed, threshold;   /* subsample != 0: on */
+    uint32_t emit;                         /* HPN_VIEW_BAM, _TEXT or _COUNT */
+    uint32_t flag_style;                   /* text: 0 decimal, 1 hexadecimal (-x), 2 letters (-X) */
+    int32_t n_targets;                     /* text: the header's targets */
+    uint32_t reserved;
+    const char *target_names;              /* text: their names behind one another, without NULs ... */
+    const uint32_t *target_name_off;       /* ... name t is bytes [off[t], off[t + 1]); n_targets + 1 entries */
+    /* the read-group rule, C strings (copied): a record WITH an RG field is decided by rg_id (-r) if given, else by the set
+     * rg_ids (-R) if has_rg_ids; a record the two leave undecided -- it has no RG field, or neither is given -- is kept only if
+     * its RG value is one of lib_ids, the IDs whose LB is the library (-l), if has_library; without the three nothing is read */
+    const char *rg_id;                     /* NULL: no -r */
+    const char *const *rg_ids;
+    const char *const *lib_ids;
+    uint32_t n_rg_ids, n_lib_ids;
+    uint32_t has_rg_ids, has_library;      /* an empty set still rules: it keeps nothing it decides */
+    uint64_t reserved2[4];                 /* 0 */
+} hpn_view_opts;
+typedef struct hpn_view_info {
+    uint64_t n_records;      /* records of this batch */
+    uint64_t store_bytes;    /* bytes the record store holds after this call */
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, reserved;
+} hpn_view_info;
+typedef struct hpn_view_result {
+    uint64_t n_records, n_out;                  /* records in, records kept */
+    uint64_t payload_bytes, text_bytes;
+    int64_t bad_record;
+    int32_t bad_tid, bad_pos;
+    uint32_t reason, reserved;
+} hpn_view_result;
+typedef struct hpn_view_text_info {
+    uint64_t n_records, n_bytes;                /* the slice's lines and their bytes */
+} hpn_view_text_info;
+int hpn_bam_view_begin(hpn_ctx *ctx, const hpn_view_opts *opts);
+int hpn_bam_view_add_raw_dev(hpn_ctx *ctx, const uint8_t *d_raw, hpn_view_info *info);
+int hpn_bam_view_finish(hpn_ctx *ctx, hpn_view_result *res);
+int hpn_bam_view_order(hpn_ctx *ctx, uint32_t *order, uint64_t n);
+int hpn_bam_view_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records, int last, hpn_split_info *info);
+int hpn_bam_view_blocks(hpn_ctx *ctx, uint64_t first, hpn_split_block *out, uint64_t cap, uint64_t *n);
+int hpn_bam_view_payload_dev(hpn_ctx *ctx, const uint8_t **d_payload, uint64_t *n_bytes);
+int hpn_bam_view_stored_dev(hpn_ctx *ctx, const uint8_t **d_image, uint64_t *n_bytes);
+int hpn_bam_view_text_emit(hpn_ctx *ctx, uint64_t first_record, uint64_t max_records, hpn_view_text_info *info);
+int hpn_bam_view_text_dev(hpn_ctx *ctx, const uint8_t **d_text, uint64_t *n_bytes);
 
 /* ---- multi-GPU reduction of count vectors -----------------------------------
  * One RCCL communicator per context; `unique_id` is the 128-byte ncclUniqueId
